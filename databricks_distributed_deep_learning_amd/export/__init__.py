@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import copy
 import os
+import tempfile
 import time
 from typing import Dict, List, Optional
 
@@ -191,9 +192,14 @@ def _ort_session(path: Optional[str]):
 
 
 def bench_runtimes(model: ResNet, x: torch.Tensor, iters: int = 50, warmup: int = 5,
-                   categories: Optional[List[str]] = None, workdir: str = "/tmp/ddl_export",
+                   categories: Optional[List[str]] = None, workdir: Optional[str] = None,
                    rtol: float = 1e-5, atol: float = 1e-4) -> Dict[str, object]:
-    """Run every available backend on ``x`` (NHWC batch) and compare with eager fp32."""
+    """Run every available backend on ``x`` (NHWC batch) and compare with eager fp32.
+
+    The exported artifacts go to ``workdir`` (default: one directory per user under the
+    system's temporary directory, so another user's earlier run never owns it)."""
+    if workdir is None:
+        workdir = os.path.join(tempfile.gettempdir(), f"ddl_export_{os.getuid()}")
     device = x.device
     model = model.eval()
     results: Dict[str, Dict[str, object]] = {}

@@ -7,6 +7,7 @@
 #   tests [FILES]         GPU test suite (default all of tests/) -> gpurun_out/test_gpu.log
 #   smoke                 __graft_entry__.smoke()             -> gpurun_out/smoke.log
 #   bench [args]          bench.py (default 20 steps, 5 warm-up) -> gpurun_out/bench.log
+#                         (bench and stock pass --full: ResNet-50 and BERT-base in one run)
 #   stock [args]          bench.py --native stock (plain PyTorch-ROCm + torch DDP arm)
 #   ab LIB MODEL [RUNS]   same-box A/B of libddl_LIB.so (scripts/build_ab.sh) vs the tree's library,
 #                         alternating RUNS times (default 3) on MODEL (resnet50 | bert_base | vit_b16 | ...)
@@ -55,10 +56,12 @@ step() {
         || { tail -20 gpurun_out/smoke.log; return 1; }
       tail -1 gpurun_out/smoke.log ;;
     bench)
+      set -- --full "$@"      # ResNet-50 and BERT-base, as in the committed bench logs
       timeout -k 10 400 python bench.py --steps 20 --warmup 5 "$@" > gpurun_out/bench.log 2>&1 \
         || { tail -20 gpurun_out/bench.log; return 1; }
       grep '^\[bench\]' gpurun_out/bench.log | cut -c1-400; tail -1 gpurun_out/bench.log ;;
     stock)
+      set -- --full "$@"
       timeout -k 10 400 python bench.py --native stock --steps 20 --warmup 5 "$@" > gpurun_out/stock.log 2>&1 \
         || { tail -20 gpurun_out/stock.log; return 1; }
       tail -1 gpurun_out/stock.log ;;
@@ -130,7 +133,7 @@ step() {
     tuneplans)
       mkdir -p gpurun_out/plans
       rm -f gpurun_out/plans/cache.json
-      for cmd in "python3 bench.py --steps 3 --warmup 5" "python3 bench.py --model vit_b16 --steps 3 --warmup 5" \
+      for cmd in "python3 bench.py --full --steps 3 --warmup 5" "python3 bench.py --model vit_b16 --steps 3 --warmup 5" \
                  "python3 bench.py --model bert_large --steps 2 --warmup 3" \
                  "$TRAIN --preset bert_large_lamb --steps 1 --warmup_steps 2 --log_every 0"; do
         # shellcheck disable=SC2086
@@ -145,7 +148,7 @@ step() {
       #   python scripts/make_plan_table.py --only-new gpurun_out/plans/preset_large.json
       ;;
     rehearse2)
-      DDL_BACKEND=gloo timeout -k 10 500 python bench.py --gpus 2 --steps 3 --warmup 1 --batch 64 --bert-batch 32 \
+      DDL_BACKEND=gloo timeout -k 10 500 python bench.py --full --gpus 2 --steps 3 --warmup 1 --batch 64 --bert-batch 32 \
         > gpurun_out/rehearse2.log 2>&1 || { tail -30 gpurun_out/rehearse2.log; return 1; }
       tail -1 gpurun_out/rehearse2.log ;;
     script)
