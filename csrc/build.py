@@ -94,13 +94,20 @@ def buildinfo_obj() -> str:
     return obj
 
 
-def compile_one(src, debug=False):
-    obj = obj_for(src)
+def flags_for(src, debug=False):
+    """The compile flags of one source: what the library, scripts/build_ab.sh and the assembly
+    checks (scripts/check_spills.py, scripts/isa_census.py) all build it with."""
     flags = list(COMMON) + EXTRA.get(os.path.basename(src), [])
     if debug:
         flags = [f for f in flags if f != "-O3"] + ["-O1", "-g"]
     if src.endswith(".cpp"):
         flags += ["-x", "hip"]
+    return flags
+
+
+def compile_one(src, debug=False):
+    obj = obj_for(src)
+    flags = flags_for(src, debug)
     cmd = [HIPCC, *flags, "-c", src, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -145,5 +152,9 @@ if __name__ == "__main__":
     ap.add_argument("--clean", action="store_true")
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("-j", "--jobs", type=int, default=min(8, os.cpu_count() or 4))
+    ap.add_argument("--flags", metavar="SRC", help="print the compile flags of one source and exit")
     a = ap.parse_args()
-    build(a.jobs, a.clean, a.debug)
+    if a.flags:
+        print(" ".join(flags_for(a.flags, a.debug)))
+    else:
+        build(a.jobs, a.clean, a.debug)

@@ -44,26 +44,13 @@ namespace {
 #ifndef DDL_GROUP_M
 #define DDL_GROUP_M 8      // tile rows per L2 group (tile order inside an XCD's share)
 #endif
-// Retire depth of the operand DMA (A/B variants, csrc/bench/gemm_stamps.cpp, profiles/gemm_stamps_dr*.log):
-//   0: the whole E / O tile is waited for at phases 4 / 8 (three half-tiles in flight);
-//   1: each half-tile is waited for in the phase right before its first read (five in flight,
-//      runtime-counted waits) -- measured 1.5-2.2x SLOWER (the counted-wait branches), kept for A/B;
-//   2 (default): phases 4 / 8 retire three halves, the fourth (staged last) two phases later --
-//      constant waits; neutral on 256-wide tiles, 10-15 % faster on 256 x 192 ones.
-#ifndef DDL_DEEP_RETIRE
-#define DDL_DEEP_RETIRE 2
-#endif
+// Retire depth of the operand DMA (csrc/bench/gemm_stamps.cpp, profiles/gemm_stamps_dr*.log): phases
+// 4 / 8 retire three halves, the fourth (staged last) two phases later -- constant waits; neutral on
+// 256-wide tiles, 10-15 % faster on 256 x 192 ones than waiting for the whole tile at phases 4 / 8.
 // Phases 1 / 5 issue the B fragments of phases 2 / 6 (quadrant (0,1)) right after their own reads
 // complete, so they land under that phase's MFMAs: the halves they read (E-B1 / O-B1) were retired
 // two phases earlier and are restaged only at phases 4 / 8; fb1 is free from phase 7 / 3 on.
-// Phases 2 / 6 then issue no fragment reads.  (DR 0 / 2 main loops, B k-contiguous only: PF_B1 in
-// gemm_big_k; 0 = read in phases 2 / 6)
-#ifndef DDL_PREFETCH_B1
-#define DDL_PREFETCH_B1 1
-#endif
-#ifndef DDL_GEMM_EPI_LDS_CODE
-#define DDL_GEMM_EPI_LDS_CODE 0   // whole-row LDS epilogue experiment (epi_lds_bf16): not compiled in
-#endif
+// Phases 2 / 6 then issue no fragment reads.  (B k-contiguous or NN: PF_B1 in gemm_big_k)
 constexpr int EP_LD = 132;   // epilogue LDS row stride (floats)
 constexpr int TB = 256, BK = 64, NTH = 512;
 constexpr int HALF = 128 * 64 * 2;   // 16 KB half-tile
@@ -105,20 +92,15 @@ struct BigParams {
     ConvDesc cd;
     int tiles_m, tiles_n;
     int ek;                   // register-epilogue variant (EK_*), set by the launcher
-    int behind_mask;          // store-behind beyond plain bf16 tiles: BEHIND_* bits (DDL_GEMM_BEHIND)
-    int epi_lds;              // DDL_GEMM_EPI_LDS=1: plain bf16 tiles stored as whole rows through LDS
     const uint8_t* bn_mask;   // ACT_BNB: BatchNorm backward reduction fused into the dgrad (gemm.hip Params)
     const float* bn_mean;
     const float* bn_istd;
     int* sched;               // persistent grid: per-XCD tile tickets (null: static tile striding)
-    int xsplit;               // split-K on a 1-D grid whose XCDs run contiguous (split, tile) runs
-    int part_bf16;            // split-K partial slabs stored as bf16 (DDL_GEMM_PART_BF16, default on)
-    int zero_b1;              // 256 x 192 NT tiles: unused B rows from the zero page (DDL_GEMM_ZB1, default on)
+    int part_bf16;            // split-K partial slabs stored as bf16 (the weight gradients'), else fp32
     int wg_tbl;               // gemm_wg_k CONVW: output-pixel row table in LDS (the split's rows fit; host)
 };
 // tile-ticket slot layout: 8 per-XCD counters + one exit counter, 128 B apart
 constexpr int SCHED_STRIDE = 32;
-enum BehindBits { BEHIND_BIAS = 1, BEHIND_GELU = 2, BEHIND_RES = 4 };
 enum EpiKind { EK_GEN = 0, EK_BF16 = 1, EK_F32 = 2, EK_GELU = 3, EK_DGELU = 4, EK_BNB = 5, EK_BNBC = 6 };
 
 __device__ __forceinline__ int half_off(int buf, int x, int h) { return ((buf * 2 + x) * 2 + h) * HALF; }
@@ -771,63 +753,6 @@ __device__ __forceinline__ void epi_direct(const BigParams& p, f32x4 (&acc)[2][2
         }
 }
 
-// Row-contiguous variant of the plain bf16 register epilogue (EK_BF16, no residual / statistics):
-// the packed tile goes through LDS one 128-row half at a time (64 KB, XOR-swizzled 16-byte chunks
-// of 512-byte rows) and every store instruction then writes whole 128-byte lines -- the register
-// epilogue's stores cover 32 bytes of a line each (two waves per line).  `stage` = 64 KB of LDS no
-// DMA is writing; raw barriers (a __syncthreads fence would drain in-flight LDS-DMA).
-__device__ __forceinline__ void epi_lds_bf16(const BigParams& p, f32x4 (&acc)[2][2][4][2], int m0, int n0, int wm,
-                                             int wn, int lane, char* stage) {
-    const int g4 = (lane >> 4) * 4, r16 = lane & 15;
-    float bv[2][2][4];
-#pragma unroll
-    for (int qn = 0; qn < 2; ++qn)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            if (p.bias) {
-                const uint2 b2 = *reinterpret_cast<const uint2*>((const bf16_t*)p.bias + n0 + qn * 128 + wn * 32 + j * 16 + g4);
-                bv[qn][j][0] = __uint_as_float(b2.x << 16);
-                bv[qn][j][1] = __uint_as_float(b2.x & 0xffff0000u);
-                bv[qn][j][2] = __uint_as_float(b2.y << 16);
-                bv[qn][j][3] = __uint_as_float(b2.y & 0xffff0000u);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) bv[qn][j][e] = 0.f;
-            }
-        }
-    const int rc = threadIdx.x & 31, rr = threadIdx.x >> 5;    // store side: 16 rows x 32 chunks per pass
-#pragma unroll
-    for (int qm = 0; qm < 2; ++qm) {
-#pragma unroll
-        for (int qn = 0; qn < 2; ++qn)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const f32x4& a = acc[qm][qn][i][j];
-                    const int r = wm * 64 + i * 16 + r16;
-                    const int c = qn * 128 + wn * 32 + j * 16 + g4;
-                    const int off = r * 512 + (((c >> 3) ^ (r & 15)) << 4) + (c & 7) * 2;
-                    *reinterpret_cast<uint2*>(stage + off) =
-                        make_uint2(pack2bf(a[0] + bv[qn][j][0], a[1] + bv[qn][j][1]),
-                                   pack2bf(a[2] + bv[qn][j][2], a[3] + bv[qn][j][3]));
-                }
-        LGKM0();
-        BARRIER();
-        uint4 v[8];
-#pragma unroll
-        for (int ps = 0; ps < 8; ++ps) {
-            const int r = ps * 16 + rr;
-            v[ps] = *reinterpret_cast<const uint4*>(stage + r * 512 + ((rc ^ (r & 15)) << 4));
-        }
-#pragma unroll
-        for (int ps = 0; ps < 8; ++ps)
-            *reinterpret_cast<uint4*>((bf16_t*)p.C + (long)(m0 + qm * 128 + ps * 16 + rr) * p.ldc + n0 + rc * 8) = v[ps];
-        LGKM0();
-        BARRIER();      // every read of this half done before the next half (or a DMA) overwrites it
-    }
-}
-
 // DIRECT: epilogue from registers (direct4) and, with it, a persistent grid: a
 // block walks tiles blockIdx.x, +gridDim.x, ...; after a tile's last MFMA it
 // stages the next tile's first K-tile, stores this tile from registers, then
@@ -835,29 +760,21 @@ __device__ __forceinline__ void epi_lds_bf16(const BigParams& p, f32x4 (&acc)[2]
 // tile's loads instead of in a chip-wide burst between waves of blocks.
 // BNB: the BatchNorm-backward epilogue variant (its own instantiation, so the extra
 // registers it needs never weigh on the other epilogues)
-// EDGE = false (DDL_GEMM_LEAN=1): every tile is interior and the epilogue kind is one of the
-// lean ones (M, N multiples of 256): the bounds-checked general epilogue is not compiled in.
-// Its 64-bit per-site addresses are what spills (35-72 VGPRs of scratch in the persistent
-// kernels); without it the NT kernel allocates spill-free -- but runs slower (see
-// edge_split_enabled), so the spills are not on the interior tiles' critical path.
 // N192: 256 x 192 tiles (register epilogue only): BERT's N = 768 / 2304 GEMMs have 192 / 576
 // tiles of 256 x 256 on 256 CUs (one 75 %-full round / 2.25 rounds); 192-wide tiles make that
 // 256 / 768 -- whole rounds.  The B operand is still staged as two 128-row halves (the rows
 // past the tile's 192 are read but never multiplied: the weight panel is L2-resident), so the
 // 8-phase schedule and its DMA counts are unchanged; quadrant qn = 1 runs one 16-column block
 // per wave (8 MFMAs instead of 16 per phase).
-template <int LA, int LB, bool KTAIL, bool DIRECT, bool BNB = false, bool EDGE = true, bool N192 = false>
+template <int LA, int LB, bool KTAIL, bool DIRECT, bool BNB = false, bool N192 = false>
 __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
     static_assert(!N192 || (DIRECT && !BNB), "192-wide tiles: register epilogue only");
     constexpr int TBN = N192 ? 192 : TB;
     constexpr bool WGRAD = LA == KO && LB == KO;   // TN: weight gradients (split-K fp32 / accumulate)
-    // B-fragment prefetch (DDL_PREFETCH_B1) where B is k-contiguous (NT, implicit-GEMM conv forward):
-    // 8192^3 NT -32 % cycles, 4096^3 -20 %; NN (transposed B reads): 4096^3 +9 % in isolation but
-    // +0.3 % on the BERT-base step (DDL_PREFETCH_B1_NN); never TN (the extra live range spilled its loop)
-#ifndef DDL_PREFETCH_B1_NN
-#define DDL_PREFETCH_B1_NN 1   // NN too: BERT-base same-box +0.3 % (9,024 vs 8,997 / 9,000, two pairs)
-#endif
-    constexpr bool PF_B1 = DDL_PREFETCH_B1 && (LB == KC || (DDL_PREFETCH_B1_NN && LA == KC && LB == KO));
+    // B-fragment prefetch where B is k-contiguous (NT, implicit-GEMM conv forward): 8192^3 NT -32 %
+    // cycles, 4096^3 -20 %; NN (transposed B reads): 4096^3 +9 % in isolation but +0.3 % on the
+    // BERT-base step; never TN (the extra live range spilled its loop)
+    constexpr bool PF_B1 = LB == KC || (LA == KC && LB == KO);
     // (+16 bytes: the tile ticket.  One LDS object only: a second __shared__ variable
     // makes the compiler's LDS-DMA alias tracking wait vmcnt(0) before fragment reads)
     __shared__ __attribute__((aligned(16))) char smem[8 * HALF + 16];
@@ -900,16 +817,16 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
     auto publish = [&]() {
         if (DYN && p.sched && threadIdx.x == 0) s_tick = tick;
     };
-    int vt = blockIdx.x, split = blockIdx.y;
+    int vt = blockIdx.x, split = 0;
 #ifdef DDL_GEMM_STAMPS
     int stamp_ti = 0;
 #endif
-    if (p.xsplit) {
+    if (p.splits > 1) {
         // split-K (one block per (tile, split), a 1-D grid): workgroups go to the XCDs round-robin,
         // so XCD x gets blocks x, x + 8, ...; they are given a CONTIGUOUS run of the split-major
         // (split, tile) order -- mostly one split's k-range over neighbouring tiles, whose A / B
         // panel rows then come from HBM once into that XCD's L2 and serve every tile that reads
-        // them (with blockIdx.y = split, an XCD's blocks spread over all splits: the TN weight
+        // them (with a (tiles, splits) grid an XCD's blocks spread over all splits: the TN weight
         // gradients streamed ~5x their unique bytes at the HBM rate)
         const int n = nwg * p.splits, xcd = blockIdx.x & 7, qn_ = n >> 3, rn = n & 7;
         const int q = (xcd < rn ? xcd * (qn_ + 1) : rn * (qn_ + 1) + (xcd - rn) * qn_) + (int)(blockIdx.x >> 3);
@@ -931,7 +848,7 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
     Stager<LA, true, KTAIL> sa;
     Stager<LB, false, KTAIL> sb;
     sa.init(p, m0);
-    sb.init(p, n0, N192 && p.zero_b1);
+    sb.init(p, n0, N192);
 
     f32x4 acc[2][2][4][2];
     auto zero_acc = [&]() {
@@ -992,69 +909,8 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
     auto vm_retire_o = [&](int hold) {
         if (hold == 22) asm volatile("s_waitcnt vmcnt(22)" ::: "memory");
         else if (hold == 30) asm volatile("s_waitcnt vmcnt(30)" ::: "memory");
-        else if (hold == 38) asm volatile("s_waitcnt vmcnt(38)" ::: "memory");
         else VM6();
     };
-#if DDL_DEEP_RETIRE == 1
-    // Counted waits from the stage-issue history: bit s of `cm` = stage slot s (the DMA of
-    // phase s + 1) of this iteration went out, `pm` = the previous iteration's slots (or the
-    // prologue's: E -> slots 1-4, O A0 / B0 / B1 -> slots 5-7).  Stage order per iteration:
-    // 1 O-A1(kO)  2 E-A0  3 E-B0  4 E-B1  5 E-A1 (kE+2)  6 O-A0  7 O-B0  8 O-B1 (kO+2).  A wait
-    // that retires the half of slot t leaves the ops younger than it in flight: 2 per issued
-    // slot after t (every wave issues 2 DMAs per half).  Half -> wait (the phase before its
-    // first read): E-B1 phase 1, E-A1 phase 2, O-A0/B0 phase 4, O-B1 phase 5, O-A1 phase 6,
-    // E-A0/B0 (next tile) phase 8.
-    auto vm_younger = [&](int n) {
-        switch (n) {
-            case 10: VMN(10); break;
-            case 8: VMN(8); break;
-            case 6: VMN(6); break;
-            case 4: VMN(4); break;
-            case 2: VMN(2); break;
-            default: VM0(); break;
-        }
-    };
-    auto younger = [&](unsigned pm, unsigned cm, int t, int q) -> int {   // slots t+1 .. q
-        const unsigned h = pm | (cm << 8);
-        const unsigned m = ((1u << (q + 1)) - 1u) & ~((1u << (t + 1)) - 1u);
-        return 2 * __builtin_popcount(h & m);
-    };
-    // fresh: the first pair after a store-behind epilogue -- E retired with the stores, O staged
-    // whole before them: retired at phase 4 by `hold` (vm_retire_o), no per-half waits
-    auto phasesE = [&](int kE, bool stO1, bool more, unsigned pm, unsigned& cm, bool fresh, int hold, bool hasO) {
-        // phase 1: E (0,0)
-        readA(0, 0);
-        readB(0, 0, fb0);
-        if (stO1) { sa.stage(p, smem, 1, 1, kE + 1); cm |= 1u; }
-        if (!fresh) vm_younger(younger(pm, cm, 3, 8));          // E-B1(kE)
-        READS_DONE_BARRIER();
-        mma(0, 0, fb0);
-        BARRIER();
-        // phase 2: E (0,1)
-        readB(0, 1, fb1);
-        if (more) { sa.stage(p, smem, 0, 0, kE + 2); cm |= 2u; }
-        if (!fresh) vm_younger(younger(pm, cm, 4, 9));          // E-A1(kE)
-        READS_DONE_BARRIER();
-        mma(0, 1, fb1);
-        BARRIER();
-        // phase 3: E (1,1)
-        readA(0, 1);
-        if (more) { sb.stage(p, smem, 0, 0, kE + 2); cm |= 4u; }
-        READS_DONE_BARRIER();
-        mma(1, 1, fb1);
-        BARRIER();
-        // phase 4: E (1,0); retire O-A0 / O-B0 (kE+1)
-        if (more) { sb.stage(p, smem, 0, 1, kE + 2); cm |= 8u; }
-        if (hasO) {
-            if (!fresh) vm_younger(younger(pm, cm, 6, 11));
-            else if (more) vm_retire_o(hold);
-            else VM0();
-        }
-        BARRIER();
-        mma(1, 0, fb0);
-        BARRIER();
-    };
-#else
     auto phasesE = [&](int kE, bool stO1, bool more, int hold = 0, bool w2 = false) {
         // phase 1: E (0,0)
         readA(0, 0);
@@ -1067,12 +923,8 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
         // phase 2: E (0,1)
         if (!PF_B1) readB(0, 1, fb1);
         if (more) sa.stage(p, smem, 0, 0, kE + 2);
-#if DDL_DEEP_RETIRE == 2
         // E-A1 (staged at the previous pair's phase 5) retired here, read in phase 3
         if (w2) { if (more) VMN(10); else VMN(8); }
-#else
-        (void)w2;
-#endif
         READS_DONE_BARRIER();
         mma(0, 1, fb1);
         BARRIER();
@@ -1083,18 +935,12 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
         mma(1, 1, fb1);
         BARRIER();
         // phase 4: E (1,0); retire O(kE+1)
-#if DDL_DEEP_RETIRE == 2
         // O-A0 / B0 / B1 only: O-A1 (staged at phase 1) is retired at phase 6
         if (more) { sb.stage(p, smem, 0, 1, kE + 2); if (hold) vm_retire_o(hold); else VMN(8); } else { VM0(); }
-#else
-        if (more) { sb.stage(p, smem, 0, 1, kE + 2); vm_retire_o(hold); } else { VM0(); }
-#endif
         BARRIER();
         mma(1, 0, fb0);
         BARRIER();
     };
-
-#endif
 
     // prologue, first part: E <- tile kt0 (all halves)
     auto prologueE = [&]() {
@@ -1109,11 +955,7 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
             sa.stage(p, smem, 1, 0, kt0 + 1);
             sb.stage(p, smem, 1, 0, kt0 + 1);
             sb.stage(p, smem, 1, 1, kt0 + 1);
-#if DDL_DEEP_RETIRE == 1
-            VMN(10);      // E-A0 / E-B0 only: E-B1 / E-A1 are retired at phases 1 / 2 (vm_younger)
-#else
             VM6();
-#endif
         } else {
             VM0();
         }
@@ -1135,49 +977,6 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
     for (;;) {
         if (nK > 0) {
             const int pairs = nK / 2;
-#if DDL_DEEP_RETIRE == 1
-            unsigned pm = nK > 1 ? 0xFEu : 0x1Eu, cm = 0u;    // the prologue's slots (see vm_younger)
-            for (int it = 0; it < pairs; ++it) {
-                KSTAMP(it);
-                const int kE = kt0 + 2 * it, kO = kE + 1;
-                const bool more = kE + 2 < kt_end;
-                const bool moreO = kO + 2 < kt_end;
-                // first pair after a store-behind epilogue: O is already staged whole
-                const bool fresh = !BNB && it == 0 && hold_o;
-                phasesE(kE, !fresh, more, pm, cm, fresh, it == 0 ? hold_o : 0, true);
-                // phase 5: O (0,0)
-                readA(1, 0);
-                readB(1, 0, fb0);
-                if (more) { sa.stage(p, smem, 0, 1, kE + 2); cm |= 16u; }
-                if (!fresh) vm_younger(younger(pm, cm, 7, 12));     // O-B1(kO)
-                READS_DONE_BARRIER();
-                mma(0, 0, fb0);
-                BARRIER();
-                // phase 6: O (0,1)
-                readB(1, 1, fb1);
-                if (moreO) { sa.stage(p, smem, 1, 0, kO + 2); cm |= 32u; }
-                if (!fresh) vm_younger(younger(pm, cm, 8, 13));     // O-A1(kO)
-                READS_DONE_BARRIER();
-                mma(0, 1, fb1);
-                BARRIER();
-                // phase 7: O (1,1)
-                readA(1, 1);
-                if (moreO) { sb.stage(p, smem, 1, 0, kO + 2); cm |= 64u; }
-                READS_DONE_BARRIER();
-                mma(1, 1, fb1);
-                BARRIER();
-                // phase 8: O (1,0); retire E-A0 / E-B0 (kE+2)
-                if (moreO) { sb.stage(p, smem, 1, 1, kO + 2); cm |= 128u; }
-                if (more) vm_younger(younger(pm, cm, 10, 15));
-                BARRIER();
-                mma(1, 0, fb0);
-                BARRIER();
-                pm = cm;
-                cm = 0u;
-            }
-            // odd tile count: the last E tile (its E-B1 / E-A1 retired at phases 1 / 2)
-            if (nK & 1) phasesE(kt_end - 1, false, false, pm, cm, false, 0, false);
-#else
             for (int it = 0; it < pairs; ++it) {
                 KSTAMP(it);
                 const int kE = kt0 + 2 * it, kO = kE + 1;
@@ -1197,13 +996,11 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
                 // phase 6: O (0,1)
                 if (!PF_B1) readB(1, 1, fb1);
                 if (moreO) sa.stage(p, smem, 1, 0, kO + 2);
-#if DDL_DEEP_RETIRE == 2
                 if (BNB || !(it == 0 && hold_o)) {        // O-A1 (phase 1), read in phase 7
                     if (moreO) VMN(10);
                     else if (more) VMN(8);
                     else VM0();
                 }
-#endif
                 READS_DONE_BARRIER();
                 mma(0, 1, fb1);
                 BARRIER();
@@ -1214,19 +1011,14 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
                 mma(1, 1, fb1);
                 BARRIER();
                 // phase 8: O (1,0); retire E(kE+2)
-#if DDL_DEEP_RETIRE == 2
                 // E-A0 / B0 / B1 only: E-A1 (phase 5) is retired at the next pair's phase 2
                 if (moreO) { sb.stage(p, smem, 1, 1, kO + 2); VMN(8); } else { VM0(); }
-#else
-                if (moreO) { sb.stage(p, smem, 1, 1, kO + 2); VM6(); } else { VM0(); }
-#endif
                 BARRIER();
                 mma(1, 0, fb0);
                 BARRIER();
             }
             // odd tile count: the last E tile (fully landed: phase 8 waited vmcnt(0))
             if (nK & 1) phasesE(kt_end - 1, false, false);
-#endif
 #if DDL_STAGGER
             // realign the groups: after this barrier every wave has finished its
             // last MFMA and every fragment read, so the LDS buffers are free
@@ -1241,7 +1033,7 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
                                              : vt + (int)gridDim.x;
             const bool next = vn < nwg;
             const int m0c = m0, n0c = n0, tm_c = tm;
-            const bool interior = !EDGE || (m0c + TB <= p.M && n0c + TBN <= p.N);
+            const bool interior = m0c + TB <= p.M && n0c + TBN <= p.N;
             // Store-behind: when this tile's epilogue issues a KNOWN number of vector-memory
             // ops (lean bf16 variant: one 8-byte store per site, +8 statistics stores), the
             // WHOLE next prologue (E and O halves) is issued first and only the E loads are
@@ -1249,23 +1041,16 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
             // loads and MFMAs instead of being waited for (vmcnt retires in issue order).
             // Short-K tiles (1x1 convolutions: K = 64..256) are otherwise latency-bound on
             // load -> compute -> store-drain per tile.
-            // (a residual's loads retire in order behind the next prologue's, so the counts
-            // below stay upper bounds)
+            // Plain bf16 tiles only: with a bias or GELU it measured neutral, with a residual -8 %
+            // (profiles/epilogue_behind_ab.log).
             // (not with 192-wide tiles: the store counts its vmcnt waits assume are the 256-wide ones)
-            // whole-row stores through LDS (buffer O's 64 KB; the next prologue is issued after them)
-            // (compiled in only with -DDDL_GEMM_EPI_LDS_CODE=1: its second prologue site raised the
-            // register pressure enough to spill the KO operand loaders' row offsets inside the main
-            // loop -- TN / NN 2x slower, profiles/gemm_spills_r04.md)
-            const bool lds_epi = DDL_GEMM_EPI_LDS_CODE && !N192 && !BNB && p.epi_lds && interior && p.ek == EK_BF16 && !p.res && !p.colstats;
-            const bool behind = !N192 && !lds_epi && next && nK > 0 && interior &&
-                ((p.ek == EK_BF16 && (!p.bias || (p.behind_mask & BEHIND_BIAS)) &&
-                  (!p.res || (p.behind_mask & BEHIND_RES))) ||
-                 (p.ek == EK_GELU && (p.behind_mask & BEHIND_GELU)));
-            if (next && !lds_epi) {
+            const bool behind = !N192 && next && nK > 0 && interior &&
+                p.ek == EK_BF16 && !p.bias && !p.res;
+            if (next) {
                 coords(vn);
                 ask();
                 sa.init(p, m0);
-                sb.init(p, n0, N192 && p.zero_b1);
+                sb.init(p, n0, N192);
                 if (nK > 0) prologueE();
                 if (behind && nK > 1) {
                     sa.stage(p, smem, 1, 0, kt0 + 1);
@@ -1278,16 +1063,7 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
             // edge tiles and the rarer epilogue options the general one
             if (BNB)   // checked on every tile: a lean interior twin spills (measured slower)
                 epi_direct<EK_BNBC>(p, acc, m0c, n0c, tm_c, wm, wn, lane, split);
-            else if (lds_epi) {
-                epi_lds_bf16(p, acc, m0c, n0c, wm, wn, lane, smem + half_off(1, 0, 0));
-                if (next) {
-                    coords(vn);
-                    ask();
-                    sa.init(p, m0);
-                    sb.init(p, n0);
-                    if (nK > 0) prologueE();
-                }
-            } else if (interior && p.ek == EK_BF16)
+            else if (interior && p.ek == EK_BF16)
                 epi_direct<EK_BF16, N192, !WGRAD>(p, acc, m0c, n0c, tm_c, wm, wn, lane, split);
             else if (interior && p.ek == EK_F32)
                 epi_direct<EK_F32, N192, true, WGRAD>(p, acc, m0c, n0c, tm_c, wm, wn, lane, split);
@@ -1295,7 +1071,7 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
                 epi_direct<EK_GELU, N192>(p, acc, m0c, n0c, tm_c, wm, wn, lane, split);
             else if (!WGRAD && interior && p.ek == EK_DGELU)   // (never a weight gradient's)
                 epi_direct<EK_DGELU, N192>(p, acc, m0c, n0c, tm_c, wm, wn, lane, split);
-            else if constexpr (EDGE)
+            else
                 epi_direct<EK_GEN, N192, true, WGRAD>(p, acc, m0c, n0c, tm_c, wm, wn, lane, split);
             STAMP(3);
 #ifdef DDL_GEMM_STAMPS
@@ -1312,15 +1088,9 @@ __global__ __launch_bounds__(NTH, 1) void gemm_big_k(BigParams p) {
             if (nK > 0) {
                 if (behind) {
                     // E landed once at most (O loads) + (epilogue stores) remain outstanding;
-                    // GELU tiles store twice per site (output + pre-activation): the 6-bit
-                    // counter's maximum is a stronger wait than needed, never a weaker one
-                    // per wave: EK_BF16 16 pair stores (+8 statistics stores), EK_GELU 32;
+                    // per wave 16 pair stores (+8 statistics stores);
                     // E retires with O (8 ops, nK > 1) and those stores younger than it
-                    if (p.ek == EK_GELU) {
-                        if (nK > 1) asm volatile("s_waitcnt vmcnt(40)" ::: "memory");
-                        else asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
-                        hold_o = nK > 1 ? 38 : 0;
-                    } else if (nK > 1) {
+                    if (nK > 1) {
                         if (p.colstats) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
                         else asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
                         hold_o = p.colstats ? 30 : 22;
@@ -1579,10 +1349,7 @@ constexpr int WG_HALF = WG_BK * 256;     // bytes: 32 k-rows x 128 columns x 2 B
 // CW: B is the implicit im2col of an NHWC input (conv weight gradient, CONVW): reduction rows are
 // output pixels, columns (tap, channel); a lane's 8 columns are one tap's 8 channels (C % 8 == 0),
 // fixed for the whole reduction, so only the pixel is decomposed per DMA (padding: the zero page)
-// NW: 4 waves (one per SIMD, 256 x 128 tiles, "wg") or 8 waves (two per SIMD, 256 x 256 tiles,
-// "wg2": the 256 x 256 kernel's operand bytes per output, the second wave on each SIMD filling the
-// first one's read / barrier gaps).  Every wave owns 128 x 64 (acc 128 registers).
-// CONVW row table (4-wave kernel): the B operand's reduction rows are output pixels, and decomposing a
+// CONVW row table: the B operand's reduction rows are output pixels, and decomposing a
 // row into (image, h, w) per DMA -- two divisions, the bounds and a 64-bit address per lane -- made the
 // conv weight gradient's loop 2.6 VALU per MFMA against 0.4 for a plain TN GEMM (15-35 % slower than
 // the same GEMM over a materialized im2col, profiles/wg_convw_r06.log).  The workgroup decomposes its
@@ -1600,8 +1367,9 @@ __device__ __forceinline__ uint2 wg_row_rec(uint32_t lds_addr) {
     return v;
 }
 
-template <bool CW, int NW, bool TBL = false>
-__global__ __launch_bounds__(NW * 64, 1) void gemm_wg_k(BigParams p) {
+template <bool CW, bool TBL = false>
+__global__ __launch_bounds__(256, 1) void gemm_wg_k(BigParams p) {
+    constexpr int NW = 4;                                        // one wave per SIMD, 128 x 64 each
     constexpr int WN = NW / 2, TNW = 64 * WN, BH = TNW / 128;   // waves along N, tile N, B halves
     constexpr int JW = 8 / NW;                                   // DMA instructions per wave per half
     constexpr int DMA = JW * (2 + BH);                           // ... per k-tile
@@ -1802,50 +1570,10 @@ int num_cus() {
     return n;
 }
 
-// DDL_GEMM_DIRECT=0 forces the LDS-staged epilogue everywhere (A/B timing, tests)
-bool direct_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("DDL_GEMM_DIRECT");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// DDL_GEMM_LEAN=1 routes all-interior GEMMs to the variant without the general epilogue.
-// Off by default: spill-free as it is (the NT kernel), it measured 1.9 % SLOWER on BERT-base
-// same-box (8318-8333 vs 8473-8491 samples/s, 3 alternating runs each) -- the scratch the
-// general epilogue costs sits off the interior tiles' path, and the allocation the lean
-// variant gets in exchange schedules the main loop worse.
-bool edge_split_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("DDL_GEMM_LEAN");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
-
-// DDL_GEMM_XSPLIT=0: split-K grids as (tiles, splits) with blockIdx.y = split (A/B timing)
-bool xsplit_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("DDL_GEMM_XSPLIT");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
 // DDL_GEMM_DYNAMIC=0 keeps the static tile striding of the persistent grid (A/B timing)
 bool dynamic_enabled() {
     static const bool on = [] {
         const char* e = getenv("DDL_GEMM_DYNAMIC");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// DDL_GEMM_PERSIST=0: one block per tile (grid = tiles) instead of one persistent block per CU (A/B)
-bool persist_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("DDL_GEMM_PERSIST");
         return !(e && e[0] == '0');
     }();
     return on;
@@ -1875,50 +1603,8 @@ int* sched_slot(hipStream_t st) {
     return base[dev] + (size_t)(next[dev]++ % SLOTS) * SLOT_INTS;
 }
 
-// DDL_GEMM_BEHIND: BEHIND_* bits -- which register epilogues besides plain bf16 let
-// their stores drain under the next tile's prologue.  Measured neutral (bias, GELU:
-// profiles/epilogue_behind_ab.log) to -8 % (residual), so all off by default
-int behind_mask() {
-    static const int m = [] {
-        const char* e = getenv("DDL_GEMM_BEHIND");
-        return e ? atoi(e) : 0;
-    }();
-    return m;
-}
-
-// DDL_GEMM_PART_BF16=0: split-K partial slabs in fp32 (default bf16: each partial is a fp32 sum of
-// its k-range rounded once; the reduce sums them in fp32 -- half the slab bytes on both sides)
-bool part_bf16_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("DDL_GEMM_PART_BF16");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// DDL_GEMM_ZB1=0: 256 x 192 NT tiles stage all 256 B rows (the 64 past the tile read, never used) (A/B)
-bool zero_b1_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("DDL_GEMM_ZB1");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// DDL_GEMM_EPI_LDS=1: plain bf16 interior tiles store whole rows through LDS (epi_lds_bf16)
-bool epi_lds_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("DDL_GEMM_EPI_LDS");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
-
 template <int LA, int LB>
 int launch_big(BigParams& p, float* ws, long ws_elems, int splits, hipStream_t st, bool n192 = false) {
-    p.behind_mask = behind_mask();
-    p.epi_lds = epi_lds_enabled() ? 1 : 0;
-    p.zero_b1 = zero_b1_enabled() ? 1 : 0;
     const int tbn = n192 ? 192 : TB;
     p.tiles_m = (p.M + TB - 1) / TB;
     p.tiles_n = (p.N + tbn - 1) / tbn;
@@ -1944,7 +1630,7 @@ int launch_big(BigParams& p, float* ws, long ws_elems, int splits, hipStream_t s
     const bool ktail = (p.K % BK) != 0 || ((LA == CONV || LB == CONVW) && (p.cd.C % BK) != 0);
     // register epilogue + persistent grid when the epilogue is one direct4 covers
     // (split-K partials always: the reduce kernel applies the real epilogue)
-    const bool direct = direct_enabled() &&
+    const bool direct =
         (splits > 1 || (!p.row_remap && (p.act == ACT_NONE || p.act == ACT_RELU || p.act == ACT_GELU ||
                                           (p.act == ACT_DGELU && p.aux) || p.act == ACT_BNB)));
     if (splits > 1 || (p.out_f32 && !p.bias && p.act == ACT_NONE))
@@ -1965,7 +1651,7 @@ int launch_big(BigParams& p, float* ws, long ws_elems, int splits, hipStream_t s
     if (p.act == ACT_BNB && (!direct || splits > 1)) return -8;   // register epilogue only
     const int nwg = p.tiles_m * p.tiles_n;
     int gx = nwg;
-    if (direct && splits == 1 && persist_enabled()) {
+    if (direct && splits == 1) {
         // persistent: one block per CU walks tiles blockIdx.x, +gridDim.x, ...
         // (a multiple of 8, so a block's tiles stay on its XCD); split-K grids keep
         // one block per (tile, split) -- a capped grid would leave tiles for a second round
@@ -1973,9 +1659,8 @@ int launch_big(BigParams& p, float* ws, long ws_elems, int splits, hipStream_t s
         gx = std::min(nwg, cap);
         if (gx < nwg && p.act != ACT_BNB && dynamic_enabled()) kp.sched = sched_slot(st);
     }
-    // split-K: a 1-D grid whose XCDs each run a contiguous (split, tile) range (gemm_big_k xsplit)
-    kp.xsplit = splits > 1 && xsplit_enabled();
-    const dim3 grid(kp.xsplit ? gx * splits : gx, kp.xsplit ? 1 : splits);
+    // split-K: a 1-D grid whose XCDs each run a contiguous (split, tile) range (gemm_big_k)
+    const dim3 grid(gx * splits);
     if (direct) {
         if constexpr (LB == KC && (LA == KC || LA == CONV)) {   // dgrad operand layouts
             if (p.act == ACT_BNB) {
@@ -1987,22 +1672,15 @@ int launch_big(BigParams& p, float* ws, long ws_elems, int splits, hipStream_t s
         if (p.act == ACT_BNB) return -8;
         if (n192) {
             if constexpr (LA == KC && (LB == KC || LB == KO)) {   // Linear fwd / dgrad operand layouts
-                if (ktail) hipLaunchKernelGGL((gemm_big_k<LA, LB, true, true, false, true, true>), grid, dim3(NTH), 0, st, kp);
-                else hipLaunchKernelGGL((gemm_big_k<LA, LB, false, true, false, true, true>), grid, dim3(NTH), 0, st, kp);
+                if (ktail) hipLaunchKernelGGL((gemm_big_k<LA, LB, true, true, false, true>), grid, dim3(NTH), 0, st, kp);
+                else hipLaunchKernelGGL((gemm_big_k<LA, LB, false, true, false, true>), grid, dim3(NTH), 0, st, kp);
             } else {
                 return -9;
             }
-        } else {
-        // all tiles interior with a lean epilogue kind: the variant without the general epilogue
-        const bool lean = p.M % TB == 0 && p.N % TB == 0 && p.ek != EK_GEN && edge_split_enabled();
-        if (lean) {
-            if (ktail) hipLaunchKernelGGL((gemm_big_k<LA, LB, true, true, false, false>), grid, dim3(NTH), 0, st, kp);
-            else hipLaunchKernelGGL((gemm_big_k<LA, LB, false, true, false, false>), grid, dim3(NTH), 0, st, kp);
         } else if (ktail) {
             hipLaunchKernelGGL((gemm_big_k<LA, LB, true, true>), grid, dim3(NTH), 0, st, kp);
         } else {
             hipLaunchKernelGGL((gemm_big_k<LA, LB, false, true>), grid, dim3(NTH), 0, st, kp);
-        }
         }
     } else {
         if (n192) return -9;    // 192-wide tiles: register epilogue only
@@ -2060,13 +1738,11 @@ DDL_API int ddl_gemm_big2(int mode, const void* A, long lda, const void* B, long
 // applies accumulate / the output dtype.  Returns -1 when the shape is outside the kernel's contract.
 // conv (nullable): the CONVW descriptor (as ddl_gemm_big2) -- B is then the NHWC input and C the
 // weight gradient [Cout][R * S * Cin] (channel count % 8 == 0); zero: >= 16 zero bytes (padding taps)
-// wide: 8 waves on 256 x 256 tiles ("wg2", N % 256 == 0) instead of 4 on 256 x 128 ("wg")
 DDL_API int ddl_gemm_wgrad(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
                            int out_f32, int splits, float* workspace, long ws_elems, int accumulate,
-                           const int* conv, const void* zero, int wide, hipStream_t st) {
+                           const int* conv, const void* zero, hipStream_t st) {
     if (M <= 0 || N <= 0) return 0;
-    const int tnw = wide ? 256 : 128;
-    if (M % 256 || N % tnw || K <= 0 || K % (4 * WG_BK) || lda % 8 || ldb % 8 || ldc % 4 || ldc < N ||
+    if (M % 256 || N % 128 || K <= 0 || K % (4 * WG_BK) || lda % 8 || ldb % 8 || ldc % 4 || ldc < N ||
         ((uintptr_t)A & 15) || ((uintptr_t)B & 15) || (conv && (conv[3] % 8 || !zero)))
         return -1;
     BigParams p{};
@@ -2076,7 +1752,7 @@ DDL_API int ddl_gemm_wgrad(const void* A, long lda, const void* B, long ldb, voi
     p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
     p.act = ACT_NONE; p.accumulate = accumulate; p.out_f32 = out_f32;
     p.tiles_m = M / 256;
-    p.tiles_n = N / tnw;
+    p.tiles_n = N / 128;
     const int nkt = K / WG_BK;                    // a multiple of 4 (K % 128 == 0)
     if (splits < 1) splits = 1;
     if (splits > nkt / 4) splits = nkt / 4;
@@ -2084,22 +1760,17 @@ DDL_API int ddl_gemm_wgrad(const void* A, long lda, const void* B, long ldb, voi
     splits = (nkt + p.kt_per_split - 1) / p.kt_per_split;
     p.splits = splits;
     p.split_stride = (long)M * ldc;
-    p.part_bf16 = !out_f32 && part_bf16_enabled() ? 1 : 0;
+    p.part_bf16 = !out_f32;   // bf16 slabs: half the bytes written here and read by the reduce
     // the row table: the split's rows fit behind the ring and every element offset fits 31 bits
-    p.wg_tbl = conv && !wide && (long)p.kt_per_split * WG_BK * 8 <= WG_TBL_BYTES &&
+    p.wg_tbl = conv && (long)p.kt_per_split * WG_BK * 8 <= WG_TBL_BYTES &&
                (long)conv[0] * conv[1] * conv[2] * conv[3] < (1L << 31) && conv[1] < 32768 && conv[2] < 32768;
     if (!workspace || ws_elems < p.split_stride * splits) return -2;
     BigParams kp = p;
     kp.C = workspace;
     const dim3 grid(p.tiles_m * p.tiles_n * splits);
-    if (wide) {
-        if (conv) hipLaunchKernelGGL((gemm_wg_k<true, 8>), grid, dim3(512), 0, st, kp);
-        else hipLaunchKernelGGL((gemm_wg_k<false, 8>), grid, dim3(512), 0, st, kp);
-    } else {
-        if (conv && p.wg_tbl) hipLaunchKernelGGL((gemm_wg_k<true, 4, true>), grid, dim3(256), 0, st, kp);
-        else if (conv) hipLaunchKernelGGL((gemm_wg_k<true, 4>), grid, dim3(256), 0, st, kp);
-        else hipLaunchKernelGGL((gemm_wg_k<false, 4>), grid, dim3(256), 0, st, kp);
-    }
+    if (conv && p.wg_tbl) hipLaunchKernelGGL((gemm_wg_k<true, true>), grid, dim3(256), 0, st, kp);
+    else if (conv) hipLaunchKernelGGL((gemm_wg_k<true>), grid, dim3(256), 0, st, kp);
+    else hipLaunchKernelGGL((gemm_wg_k<false>), grid, dim3(256), 0, st, kp);
     launch_reduce(p, workspace, st);
     return (int)hipGetLastError();
 }

@@ -74,7 +74,6 @@ struct DuoParams {
     int splits, kt_per_split;
     bf16_t* ws;
     int accumulate;
-    int nt_store;       // DDL_DUO_NT bits (A/B timing): 1 = the pre-activation (aux) image, 2 = C, stored non-temporal
     const bf16_t* zero; // LCONV: 16 zero bytes (g_duo_zero), the source of padding pixels
 };
 
@@ -499,7 +498,10 @@ __global__ __launch_bounds__(NTH, 2) void gemm_duo_k(DuoParams p) {
         return;
     }
     if (EK == E_GELU && p.aux) {
-        store_image(p.aux, p.ldc, cbytes, false, (p.nt_store & 1) != 0);
+        // the pre-activation (read again only by the backward) leaves non-temporal -- BERT-base
+        // +0.25-0.35 % same-box (profiles/duo_nt_ab.log); the GELU output (the next GEMM's operand)
+        // keeps the default policy
+        store_image(p.aux, p.ldc, cbytes, false, true);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         BARRIER();                                     // every image read done before it is rewritten
 #pragma unroll
@@ -508,7 +510,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_duo_k(DuoParams p) {
             for (int j = 0; j < 4; ++j)
                 *reinterpret_cast<uint2*>(smem + img_off(i, j)) = make_uint2(yk[i][j][0], yk[i][j][1]);
     }
-    store_image(p.C, p.ldc, cbytes, p.accumulate != 0, (p.nt_store & 2) != 0);
+    store_image(p.C, p.ldc, cbytes, p.accumulate != 0);
 }
 
 // split-K reduce of the weight-gradient path: C (+)= sum of the bf16 partial tiles, 8 columns per
@@ -601,11 +603,6 @@ DDL_API int ddl_gemm_duo(int mode, const void* A, long lda, const void* B, long 
     p.bias = (const bf16_t*)bias; p.res = (const bf16_t*)res; p.aux = (bf16_t*)aux; p.colstats = colstats;
     p.bn_mask = bn.mask; p.bn_mean = bn.mean; p.bn_istd = bn.istd;
     p.splits = 1;
-    // default 1: the pre-activation (read again only by the backward) leaves non-temporal --
-    // BERT-base +0.25-0.35 % same-box (profiles/duo_nt_ab.log); the GELU output (the next GEMM's
-    // operand) keeps the default policy
-    static const int nt_bits = getenv("DDL_DUO_NT") ? atoi(getenv("DDL_DUO_NT")) : 1;
-    p.nt_store = nt_bits;
     p.kt_per_split = K / DBK;
     p.tiles_m = (M + TM - 1) / TM;
     p.tiles_n = N / TN;

@@ -15,7 +15,7 @@ from ._lib import I, L, P
 _lib.register({"ddl_gemm": [I, P, L, P, L, P, L, I, I, I, P, I, I, P, I, I, P, L, P, I, P, I, P, P],
                "ddl_gemm_n64": [I, P, L, P, L, P, L, I, I, I, P, I, I, P, I, I, P, L, P, I, P, I, P, P],
                "ddl_gemm_big2": [I, P, L, P, L, P, L, I, I, I, P, I, I, P, I, I, P, L, P, I, P, I, P, P, P],
-               "ddl_gemm_wgrad": [P, L, P, L, P, L, I, I, I, I, I, P, L, I, P, P, I, P],
+               "ddl_gemm_wgrad": [P, L, P, L, P, L, I, I, I, I, I, P, L, I, P, P, P],
                "ddl_stream_wgrad": [P, L, P, L, P, L, I, I, L, I, P, L, P, I, P],
                "ddl_gemm_duo": [I, P, L, P, L, P, L, I, I, I, P, I, P, P, P, P, P],
                "ddl_gemm_duo_tn": [P, L, P, L, P, L, I, I, I, I, I, P, L, P],
@@ -40,7 +40,7 @@ def set_big_gemm(enabled: bool) -> None:
 
 
 _forced: Optional[str] = None
-_KINDS = ("big", "big192", "hybrid", "small", "narrow", "tnarrow", "wg", "wg2", "swg", "duo")
+_KINDS = ("big", "big192", "hybrid", "small", "narrow", "tnarrow", "wg", "swg", "duo")
 # per-call device timing for diagnostics (scripts/debug/gemm_trace.py): list of
 # (signature, (kernel, splits), start event, end event) while enabled
 _trace: Optional[list] = None
@@ -107,14 +107,14 @@ def pick_splits(M: int, N: int, K: int, force: Optional[int] = None) -> int:
     return max(1, min(2 * NUM_CU // tiles, nk // 8))
 
 
-_HYBRID = os.environ.get("DDL_GEMM_HYBRID", "1") != "0"   # tuner candidate (A/B: 0 = never)
 # tuner candidate "big192" (256 x 192 tiles; DDL_GEMM_192=0 drops it): whole rounds where 256-wide
 # tiles leave a partial one (N = 768 / 2304 at M = 16384: 256 / 768 tiles instead of 192 / 576).  With
-# the retire depth 2 main loop (gemm_big.hip DDL_DEEP_RETIRE) its half-filled quadrant-1 phases no
+# the main loop's staggered retire (gemm_big.hip) its half-filled quadrant-1 phases no
 # longer cost as much as full ones: 16384x768x768 NT 27.2 vs 34.6 us, 16384x2304x768 72.1 vs 95.1 us
-# (profiles/gemm_stamps_dr2.log); forcing: kernel="big192".
+# (profiles/gemm_stamps_dr2.log); forcing: kernel="big192".  (tests/test_gemm_plan_cpu.py flips it)
 _BIG192 = os.environ.get("DDL_GEMM_192", "1") == "1"
-_DIRECT = os.environ.get("DDL_GEMM_DIRECT", "1") != "0"    # gemm_big.hip register epilogue (big192 needs it)
+
+
 def hybrid_rows(M: int, N: int, K: int):
     """Row split of a 256x256-tile GEMM whose tile grid ends in a partial round, or None.
 
@@ -200,16 +200,15 @@ def _launch(kind: str, s: int, mode: int, A, lda, B, ldb, C, ldc, M, N, K, bias,
                 raise RuntimeError(f"ddl_gemm_duo(mode={mode}, M={M}, N={N}, K={K}) failed: {rc}")
             return
         kind, s = _heuristic(mode, M, N, K, row_remap, lda, ldb)   # a cached choice outside its contract
-    if kind in ("wg", "wg2"):
+    if kind == "wg":
         cw = mode == MODE_CONVW and conv_arr is not None and conv_arr[3] % 8 == 0
-        wide = kind == "wg2"
         if ((mode == MODE_TN or cw) and bias is None and act is None and residual is None and colstats is None
-                and not row_remap and wg_ok(M, N, K, lda, ldb, wide) and ldc % 4 == 0
+                and not row_remap and wg_ok(M, N, K, lda, ldb) and ldc % 4 == 0
                 and A.data_ptr() % 16 == 0 and B.data_ptr() % 16 == 0):
             ws = torch.empty(max(1, s) * M * ldc, dtype=torch.float32, device=C.device)
             rc = _lib.fn("ddl_gemm_wgrad")(A.data_ptr(), lda, B.data_ptr(), ldb, C.data_ptr(), ldc, M, N, K, out_f32,
                                            s, ws.data_ptr(), ws.numel(), int(accumulate),
-                                           conv_arr if cw else None, _zero_page(C.device).data_ptr(), int(wide),
+                                           conv_arr if cw else None, _zero_page(C.device).data_ptr(),
                                            _lib.stream())
             if rc != 0:
                 raise RuntimeError(f"ddl_gemm_wgrad(M={M}, N={N}, K={K}, splits={s}) failed: {rc}")
@@ -256,47 +255,32 @@ def _candidates(mode: int, M: int, N: int, K: int, row_remap: bool, lda: int, ld
         out += [("narrow", s) for s in sorted({1, max(1, ns // 2), ns})]
     if _WG and plain and wg_ok(M, N, K, lda, ldb) and (
             mode == MODE_TN or (mode == MODE_CONVW and conv_c is not None and conv_c % 8 == 0)):
-        # weight-gradient kernel (gemm_big.hip gemm_wg_k): 4 waves on 256x128 tiles ("wg") and 8 waves on
-        # 256x256 tiles ("wg2"); fp32 partials + reduce
+        # weight-gradient kernel (gemm_big.hip gemm_wg_k): 4 waves on 256x128 tiles; partials + reduce
         ws_ = big_splits(M, 2 * N, K)      # 256x128 tiles = 256x256 tiles on 2N
         out += [("wg", s) for s in sorted({max(1, ws_ // 2), ws_, 2 * ws_})]
-        if _WG2 and N % 256 == 0:
-            w2 = big_splits(M, N, K)
-            out += [("wg2", s) for s in sorted({max(1, w2 // 2), w2, 2 * w2})]
-    if _DUO and mode == MODE_TN and plain and not row_remap and duo_tn_ok(M, N, K, lda, ldb):
+    if mode == MODE_TN and plain and not row_remap and duo_tn_ok(M, N, K, lda, ldb):
         # dual-workgroup kernel, k-outer A: bf16 partial tiles + one reduce (split 1: straight into C)
         ds = duo_tn_splits(M, N, K)
         out += [("duo", s) for s in sorted({max(1, ds // 2), ds, min(2 * ds, K // 32)})]
-    if _SWG and mode == MODE_TN and plain and not row_remap and swg_ok(M, N, K, lda, ldb):
+    if mode == MODE_TN and plain and not row_remap and swg_ok(M, N, K, lda, ldb):
         # streaming weight gradient (stream_gemm.hip stream_wgrad_k): every workgroup owns the whole
         # M x N output over a range of K rows (no operand re-reads), bf16 partials + one reduce
         out.append(("swg", 1))
     if mode in (MODE_TN, MODE_CONVW) and plain and (M <= 192 or M % 128 == 64):
         ts = pick_splits(N, 2 * M, K)     # transposed: N' = M (output channels) on 64-wide tiles
         out += [("tnarrow", s) for s in sorted({1, max(1, ts // 2), ts})]
-    if mode in (MODE_NT, MODE_NN) and not row_remap and _big_allowed(mode, K, lda, ldb) and N % 192 == 0 \
-            and _DIRECT:
+    if mode in (MODE_NT, MODE_NN) and not row_remap and _big_allowed(mode, K, lda, ldb) and N % 192 == 0:
         # 256 x 192 tiles: whole rounds where 256-wide ones leave a partial one (N = 768: 192 -> 256 tiles
         # at M = 16384); register epilogue only (the caller drops it for the BatchNorm-backward epilogue)
         out += [("big192", 1)] if _BIG192 else []
-    if _HYBRID and mode in (MODE_NT, MODE_NN) and not row_remap and _big_allowed(mode, K, lda, ldb):
+    if mode in (MODE_NT, MODE_NN) and not row_remap and _big_allowed(mode, K, lda, ldb):
         hy = hybrid_rows(M, N, K)
         if hy is not None:                # a partial last round of 256x256 tiles
             out += [("hybrid", s) for s in sorted({2, max(2, hy[1] // 2), hy[1]})]
     return out
 
 
-_WG = os.environ.get("DDL_GEMM_WG", "1") != "0"   # tuner candidate "wg" (A/B: 0 = never)
-# "wg2" (8 waves, 256x256 tiles) is opt-in: at two waves per SIMD its 128x64 wave tiles plus fragments
-# exceed the 256-register budget and spill in the loop -- slower than both "wg" and the 256x256 kernel
-# on every BERT-base weight gradient (profiles/tn_kinds_r04_wg2.log)
-_WG2 = os.environ.get("DDL_GEMM_WG2", "0") == "1"
-
-
-_SWG = os.environ.get("DDL_GEMM_SWG", "1") != "0"   # tuner candidate "swg" (A/B: 0 = never)
-
-
-_DUO = os.environ.get("DDL_GEMM_DUO", "1") != "0"   # tuner candidate "duo" (A/B: 0 = never)
+_WG = os.environ.get("DDL_GEMM_WG", "1") != "0"   # tuner candidate "wg" (tests/test_gemm_plan_cpu.py flips it)
 
 
 def duo_ok(mode: int, M: int, N: int, K: int, lda: int, ldb: int, ldc: int, bias, act, aux, residual, colstats,
@@ -360,10 +344,9 @@ def swg_ok(M: int, N: int, K: int, lda: int, ldb: int) -> bool:
         and lda % 8 == 0 and ldb % 8 == 0 and lda >= M and ldb >= N
 
 
-def wg_ok(M: int, N: int, K: int, lda: int, ldb: int, wide: bool = False) -> bool:
-    """Shapes the weight-gradient kernel takes (ddl_gemm_wgrad's contract: 256x128 tiles, or 256x256
-    for the 8-wave ``wide`` variant "wg2")."""
-    return M % 256 == 0 and N % (256 if wide else 128) == 0 and K % 128 == 0 and K > 0 and lda % 8 == 0 \
+def wg_ok(M: int, N: int, K: int, lda: int, ldb: int) -> bool:
+    """Shapes the weight-gradient kernel takes (ddl_gemm_wgrad's contract: 256x128 tiles)."""
+    return M % 256 == 0 and N % 128 == 0 and K % 128 == 0 and K > 0 and lda % 8 == 0 \
         and ldb % 8 == 0
 
 
@@ -380,7 +363,6 @@ _tuned: dict = {}
 # candidate timings behind each tuned choice (ms per call, this process): what
 # agree_across_ranks() pools so every data-parallel rank runs the same kernel plan
 _timings: dict = {}
-_NARROW_STATS = os.environ.get("DDL_TUNE_NARROW_STATS", "0") != "0"   # same-box A/B neutral: off
 _TUNE = os.environ.get("DDL_GEMM_TUNE", "1") != "0"
 # DDL_GEMM_PREFER=kind[:factor]: take `kind` when it is within `factor` of the fastest candidate.  Default
 # "swg:1.3": the cold-cache timing over-prices the streaming weight-gradient kernel (it streams its
@@ -629,17 +611,13 @@ def _tune_candidates(mode, M, N, K, lda, ldb, bias, act, aux, row_remap, residua
     cands = _candidates(mode, M, N, K, row_remap, lda, ldb, plain, conv_c)
     if act not in (None, "relu", "gelu", "dgelu") or (act == "dgelu" and aux is None):
         cands = [c for c in cands if c[0] != "big192"]     # LDS-staged epilogue: 256-wide tiles only
-    if _DUO and duo_ok(mode, M, N, K, lda, ldb, N, bias, act, aux, residual, colstats, row_remap, conv_c):
+    if duo_ok(mode, M, N, K, lda, ldb, N, bias, act, aux, residual, colstats, row_remap, conv_c):
         cands.append(("duo", 1))
     if act == "dgelu" and colstats is not None:
         # dGELU column sums: register epilogues only (256x256 / 256x192 / dual-workgroup kernels)
         cands = [c for c in cands if c[0] in ("big", "big192", "duo")]
     if colstats is not None:   # statistics epilogue: whole-K tiles only
         cands = [c for c in cands if c[1] == 1 and not c[0].startswith("t")]
-        # 128x64 tiles (three blocks per CU) for the epilogue-heavy statistics / BN-backward
-        # tiles even where N is a multiple of 128 (more blocks in flight per CU)
-        if _NARROW_STATS and N % 64 == 0 and ("narrow", 1) not in cands:
-            cands.append(("narrow", 1))
     return cands
 
 
@@ -764,7 +742,7 @@ def _choose(mode, A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, splits, conv,
             kernel, colstats, bnb=None, online_ok: bool = False):
     """(kernel kind, splits) for one GEMM call: forced, explicit, tuned (cached) or heuristic."""
     kernel = kernel or _forced
-    if kernel == "big192" and not (mode in (MODE_NT, MODE_NN) and not row_remap and _DIRECT and
+    if kernel == "big192" and not (mode in (MODE_NT, MODE_NN) and not row_remap and
                                    _big_allowed(mode, K, lda, ldb) and act in (None, "relu", "gelu", "dgelu")
                                    and not (act == "dgelu" and aux is None)):
         kernel = "big"                    # 192-wide tiles: NT / NN with a register epilogue only
@@ -783,10 +761,10 @@ def _choose(mode, A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, splits, conv,
             choice = ("big", 1 if row_remap else (splits or big_splits(M, N, K)))
         elif kernel == "narrow":
             choice = ("narrow", 1 if row_remap else pick_splits(M, 2 * N, K, splits))
-        elif kernel in ("wg", "wg2") \
+        elif kernel == "wg" \
                 and (mode == MODE_TN or (mode == MODE_CONVW and conv is not None and conv[3] % 8 == 0)) \
                 and bias is None and act is None and residual is None and not row_remap and colstats is None \
-                and wg_ok(M, N, K, lda, ldb, kernel == "wg2"):
+                and wg_ok(M, N, K, lda, ldb):
             choice = (kernel, splits or big_splits(M, N, K))
         elif kernel == "duo" and mode == MODE_TN and bias is None and act is None and residual is None \
                 and colstats is None and not row_remap and duo_tn_ok(M, N, K, lda, ldb, ldc):

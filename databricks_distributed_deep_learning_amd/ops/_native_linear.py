@@ -347,7 +347,7 @@ def _colsum_rows(dy, act, N):
 def _dgelu_fusable(K: int) -> bool:
     """dGELU + column sums exist on the 256x256 kernel's register epilogue only."""
     from . import _native_gemm as NG
-    return os.environ.get("DDL_GEMM_DIRECT", "1") != "0" and NG._big_allowed(MODE_NT, K) and K % 4 == 0
+    return NG._big_allowed(MODE_NT, K) and K % 4 == 0
 
 
 class _DgeluHandoff:

@@ -19,8 +19,9 @@ for src in "$@"; do
   case $src in *.h) continue;; esac
   b=$(basename "$src")
   git -C "$root" show "$rev:$src" > "$tmp/$b"
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I "$tmp/include" -I "$root/csrc/include" -Wno-unused-result \
-      -ffp-contract=fast -munsafe-fp-atomics -c "$tmp/$b" -o "$tmp/$b.o"
+  # the library's own flags for this source (csrc/build.py: per-source extras included)
+  read -r -a flags <<< "$(python "$root/csrc/build.py" --flags "$b")"
+  /opt/rocm/bin/hipcc -I "$tmp/include" "${flags[@]}" -c "$tmp/$b" -o "$tmp/$b.o"
   swap[$b.o]=$tmp/$b.o
 done
 objs=()

@@ -17,15 +17,14 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PAT = re.compile(r"\n(_ZN\w*gemm_(?:big|wg)_k\w*):[^\n]*\n(.*?)\.Lfunc_end", re.S)
-TPL = re.compile(r"gemm_big_kILi(\d)ELi(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)E")
+TPL = re.compile(r"gemm_big_kILi(\d)ELi(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)E")
 
 
 def emit(src: str, out: str, defines) -> None:
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-I",
-           os.path.join(ROOT, "csrc", "include"), "-ffp-contract=fast", "-munsafe-fp-atomics", "-x", "hip",
-           "--cuda-device-only", "-S", src, "-o", out] + [f"-D{d}" for d in defines]
-    if os.path.basename(src) == "gemm_big.hip":     # the library's flags for it (csrc/build.py EXTRA)
-        cmd += ["-mllvm", "-amdgpu-mfma-vgpr-form"]
+    sys.path.insert(0, os.path.join(ROOT, "csrc"))
+    import build  # noqa: E402  (csrc/build.py: the library's flags for this source)
+    cmd = [build.HIPCC, *build.flags_for(src), "-x", "hip", "--cuda-device-only", "-S", src, "-o", out] + \
+        [f"-D{d}" for d in defines]
     subprocess.run(cmd, check=True)
 
 
@@ -68,7 +67,7 @@ def main() -> int:
     with open(path) as f:
         rows = scan(f.read())
     bad = 0
-    print("instantiation <LA LB KTAIL DIRECT BNB EDGE N192>  mfma  scratch  scratch-in-main-loop")
+    print("instantiation <LA LB KTAIL DIRECT BNB N192>  mfma  scratch  scratch-in-main-loop")
     for tag, nmf, nsc, loop in rows:
         flag = "  <-- spills in the main loop" if loop > a.max_loop else ""
         bad += bool(flag)

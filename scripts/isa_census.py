@@ -27,9 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def compile_asm(src: str, out: str) -> None:
     sys.path.insert(0, os.path.join(ROOT, "csrc"))
     import build  # noqa: E402  (csrc/build.py: the library's per-file extra flags)
-    extra = list(getattr(build, "EXTRA", {}).get(os.path.basename(src), []))
-    cmd = ["hipcc", "-O3", "--offload-arch=gfx950", "--cuda-device-only", "-S",
-           "-I" + os.path.join(ROOT, "csrc", "include"), *extra, src, "-o", out]
+    cmd = [build.HIPCC, *build.flags_for(src), "--cuda-device-only", "-S", src, "-o", out]
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
 
 
