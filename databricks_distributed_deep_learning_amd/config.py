@@ -76,6 +76,7 @@ class TrainConfig:
     data: str = "synthetic"          # synthetic (Petastorm/Delta replacement)
     synthetic_pool: int = 4          # distinct device-resident batches cycled
     pad_fraction: float = 0.0        # NLP: random right-padding up to this fraction (attention-mask path)
+    mlm_predictions: int = 0         # BERT pretraining: masked-LM prediction slots per sequence (0: none)
 
     # ---------------------------------------------------------------------
     @property
@@ -150,7 +151,7 @@ def apply_overrides(cfg: TrainConfig, argv: Optional[List[str]] = None,
     return cfg.replace(**kw)
 
 
-# The five configurations named by BASELINE.json:7-11.
+# The five configurations named by BASELINE.json:7-11, and BERT-large pretraining.
 PRESETS: Dict[str, TrainConfig] = {
     # BJ:7 — plumbing slice, CPU / gloo, world_size=2
     "resnet18_gloo": TrainConfig(model="resnet18", batch_size=8, image_size=224, steps=3,
@@ -170,6 +171,10 @@ PRESETS: Dict[str, TrainConfig] = {
     "bert_large_lamb": TrainConfig(model="bert_large", batch_size=0, seq_len=512, num_classes=2,
                                    grad_accum=4, dtype="bf16", optimizer="lamb", lr=2e-3,
                                    weight_decay=0.01, dropout=0.1),
+    # the same harness on its pretraining objective: masked LM (76 predictions per 512 tokens) + NSP
+    "bert_large_pretrain": TrainConfig(model="bert_large_pretraining", batch_size=0, seq_len=512, num_classes=2,
+                                       mlm_predictions=76, grad_accum=4, dtype="bf16", optimizer="lamb", lr=2e-3,
+                                       weight_decay=0.01, dropout=0.1),
 }
 
 

@@ -70,7 +70,12 @@ class SyntheticImageNet:
 class SyntheticTokens:
     def __init__(self, batch_size: int, seq_len: int = 128, vocab_size: int = 30522, num_labels: int = 2,
                  device: Optional[torch.device] = None, rank: int = 0, seed: int = 1234, pool: int = 4,
-                 pad_fraction: float = 0.0, steps_per_epoch: int = 0):
+                 pad_fraction: float = 0.0, steps_per_epoch: int = 0, mlm_predictions: int = 0):
+        """``mlm_predictions`` = P > 0 adds the masked-LM pretraining targets to every batch:
+        ``masked_lm_positions [B, P]`` (unique per row, ascending, inside the row's unpadded length),
+        ``masked_lm_labels [B, P]`` (a random number of trailing slots per row is padding: label
+        -100, position 0; at least one slot per row is a target) and ``next_sentence_label [B]``.
+        With 0 the batches are exactly those of a loader without the argument."""
         self.batch_size, self.seq_len = batch_size, seq_len
         self.device = device or torch.device("cpu")
         self.steps_per_epoch = steps_per_epoch
@@ -84,8 +89,29 @@ class SyntheticTokens:
                                      generator=g, device=self.device)
                 mask = (torch.arange(seq_len, device=self.device)[None, :] < lens[:, None]).to(torch.int64)
             labels = torch.randint(0, num_labels, (batch_size,), generator=g, device=self.device)
-            self.pool.append({"input_ids": ids, "attention_mask": mask, "labels": labels})
+            batch = {"input_ids": ids, "attention_mask": mask, "labels": labels}
+            if mlm_predictions > 0:
+                batch.update(self._mlm_targets(mlm_predictions, mask, vocab_size, pad_fraction, g))
+            self.pool.append(batch)
         self._i = 0
+
+    def _mlm_targets(self, P: int, mask, vocab_size: int, pad_fraction: float, g) -> dict:
+        B, S, dev = self.batch_size, self.seq_len, self.device
+        shortest = int(S * (1 - pad_fraction)) if mask is not None else S
+        if P > shortest:
+            raise ValueError(f"mlm_predictions={P} exceeds the shortest unpadded length {shortest}")
+        # P distinct positions per row: the P smallest of S random keys, padded positions keyed last
+        key = torch.rand(B, S, generator=g, device=dev)
+        if mask is not None:
+            key = key + (1 - mask).to(key.dtype) * 2.0
+        pos = key.argsort(dim=1)[:, :P].sort(dim=1).values
+        lab = torch.randint(0, vocab_size, (B, P), generator=g, device=dev)
+        n_pad = torch.randint(0, P, (B,), generator=g, device=dev)          # 0 .. P-1: one target at least
+        padded = torch.arange(P, device=dev)[None, :] >= (P - n_pad)[:, None]
+        lab = lab.masked_fill(padded, -100)
+        pos = pos.masked_fill(padded, 0)
+        nsp = torch.randint(0, 2, (B,), generator=g, device=dev)
+        return {"masked_lm_positions": pos, "masked_lm_labels": lab, "next_sentence_label": nsp}
 
     def __iter__(self):
         n = 0

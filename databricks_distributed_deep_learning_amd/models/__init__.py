@@ -5,6 +5,7 @@ import torch.nn as nn
 
 from .resnet import ResNet, resnet18, resnet34, resnet50, resnet101, resnet152  # noqa: F401
 from .bert import BertConfig, BertForSequenceClassification, bert_base, bert_large, bert_tiny  # noqa: F401
+from .bert import BertForPreTraining, bert_base_pretraining, bert_large_pretraining, bert_tiny_pretraining  # noqa: F401
 from .vit import ViTConfig, ViTForImageClassification, vit_b16  # noqa: F401
 from .layers import cast_params, convert_sync_batchnorm  # noqa: F401
 
@@ -12,6 +13,8 @@ _REGISTRY = {
     "resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50,
     "resnet101": resnet101, "resnet152": resnet152,
     "bert_base": bert_base, "bert_large": bert_large, "bert_tiny": bert_tiny,
+    "bert_base_pretraining": bert_base_pretraining, "bert_large_pretraining": bert_large_pretraining,
+    "bert_tiny_pretraining": bert_tiny_pretraining,
     "vit_b16": vit_b16,
 }
 
@@ -23,6 +26,8 @@ def available_models():
 def build_model(name: str, num_classes: int = 1000, dropout: float = 0.1, image_size: int = 224) -> nn.Module:
     if name not in _REGISTRY:
         raise KeyError(f"unknown model {name!r}; have {available_models()}")
+    if name.startswith("bert") and name.endswith("_pretraining"):
+        return _REGISTRY[name](dropout=dropout)      # MLM + NSP heads: no label count
     if name.startswith("bert"):
         return _REGISTRY[name](num_labels=num_classes, dropout=dropout)
     if name.startswith("vit"):

@@ -1,4 +1,4 @@
-"""BERT-base / BERT-large encoder + sequence-classification head (post-LN).
+"""BERT-base / BERT-large encoder + sequence-classification or pretraining (MLM + NSP) heads (post-LN).
 
 Parameter-for-parameter equivalent to HF ``BertForSequenceClassification``
 (109,483,778 params for base with 2 labels) except that Q, K and V are one fused
@@ -145,6 +145,61 @@ class BertForSequenceClassification(nn.Module):
         return logits
 
 
+class BertForPreTraining(nn.Module):
+    """BERT with the two pretraining heads (HF ``BertForPreTraining``, 110,106,428 parameters for
+    base): masked-LM -- transform (dense + GELU, LayerNorm), then a decoder whose weight IS the word
+    embedding table (tied; registered once, under the embedding) with its own bias -- and
+    next-sentence prediction on the pooled output.
+
+    ``masked_lm_positions [B, P]`` (a fixed P per batch; padded slots carry label -100 and
+    conventionally position 0): only those ``B * P`` rows are gathered and run through the MLM head,
+    so the ``[rows, vocab]`` logits cover P rows per sequence instead of S.  Valid positions must be
+    unique within a sequence (``ops.gather_rows``).  Without positions ``masked_lm_labels`` is
+    ``[B, S]`` (HF style, -100 = not a target) and the head runs on every token.
+
+    Returns ``(loss, (mlm_logits, nsp_logits))``: the loss is the sum of the objectives whose
+    labels are given (None without any); ``mlm_logits`` is None whenever MLM labels are given -- the
+    fused head (``ops.linear_cross_entropy``) never hands out the vocabulary-wide logits."""
+
+    def __init__(self, c: BertConfig):
+        super().__init__()
+        self.config = c
+        self.bert = BertModel(c)
+        H, std = c.hidden_size, c.initializer_range
+        self.mlm_dense = Linear(H, H, act="gelu", init_std=std)
+        self.mlm_ln = LayerNorm(H, c.layer_norm_eps)
+        self.mlm_bias = nn.Parameter(torch.zeros(c.vocab_size))
+        self.seq_relationship = Linear(H, 2, init_std=std)
+        nn.init.zeros_(self.mlm_dense.bias)
+        nn.init.zeros_(self.seq_relationship.bias)
+
+    @property
+    def decoder_weight(self) -> nn.Parameter:
+        # looked up on use: ``cast_params`` / ``.to()`` may replace the Parameter object
+        return self.bert.embeddings.word_embeddings.weight
+
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, masked_lm_positions=None,
+                masked_lm_labels=None, next_sentence_label=None):
+        h, pooled = self.bert(input_ids, attention_mask, token_type_ids)
+        nsp_logits = self.seq_relationship(pooled)
+        labels = masked_lm_labels.reshape(-1) if masked_lm_labels is not None else None
+        if masked_lm_positions is not None:
+            rows = ops.gather_rows(h, masked_lm_positions, labels, -100)
+        else:
+            rows = h.reshape(-1, h.shape[-1])
+        t = self.mlm_ln(self.mlm_dense(rows))
+        loss = mlm_logits = None
+        if labels is not None:
+            loss = ops.linear_cross_entropy(t, self.decoder_weight, self.mlm_bias, labels, -100,
+                                            defer_weight_ready=True)
+        else:
+            mlm_logits = ops.linear(t, self.decoder_weight, self.mlm_bias)
+        if next_sentence_label is not None:
+            nsp = ops.cross_entropy(nsp_logits, next_sentence_label)
+            loss = nsp if loss is None else loss + nsp
+        return loss, (mlm_logits, nsp_logits)
+
+
 def bert_base(num_labels: int = 2, dropout: float = 0.1, **kw) -> BertForSequenceClassification:
     return BertForSequenceClassification(BertConfig.base(num_labels=num_labels, hidden_dropout_prob=dropout,
                                                          attention_probs_dropout_prob=dropout, **kw))
@@ -164,7 +219,36 @@ def bert_tiny(num_labels: int = 2, dropout: float = 0.1, **kw) -> BertForSequenc
                                                     attention_probs_dropout_prob=dropout, **d))
 
 
+def bert_base_pretraining(dropout: float = 0.1, **kw) -> BertForPreTraining:
+    return BertForPreTraining(BertConfig.base(hidden_dropout_prob=dropout, attention_probs_dropout_prob=dropout, **kw))
+
+
+def bert_large_pretraining(dropout: float = 0.1, **kw) -> BertForPreTraining:
+    return BertForPreTraining(BertConfig.large(hidden_dropout_prob=dropout, attention_probs_dropout_prob=dropout, **kw))
+
+
+def bert_tiny_pretraining(dropout: float = 0.1, **kw) -> BertForPreTraining:
+    """``bert_tiny``'s encoder with the pretraining heads (vocabulary 1024)."""
+    d = dict(hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=512,
+             vocab_size=1024, max_position_embeddings=128)
+    d.update(kw)
+    return BertForPreTraining(BertConfig(hidden_dropout_prob=dropout, attention_probs_dropout_prob=dropout, **d))
+
+
 # ------------------------------------------------------------ HF conversion
+# HF ``BertForPreTraining`` head names <-> ours (``cls.predictions.decoder.*`` is the tied embedding
+# table and ``cls.predictions.bias`` again: checked and dropped on import, re-emitted on export)
+_HF_HEAD_MAP = {
+    "cls.predictions.transform.dense.weight": "mlm_dense.weight",
+    "cls.predictions.transform.dense.bias": "mlm_dense.bias",
+    "cls.predictions.transform.LayerNorm.weight": "mlm_ln.weight",
+    "cls.predictions.transform.LayerNorm.bias": "mlm_ln.bias",
+    "cls.predictions.bias": "mlm_bias",
+    "cls.seq_relationship.weight": "seq_relationship.weight",
+    "cls.seq_relationship.bias": "seq_relationship.bias",
+}
+_HF_TIED = {"cls.predictions.decoder.weight": "bert.embeddings.word_embeddings.weight",
+            "cls.predictions.decoder.bias": "cls.predictions.bias"}
 _HF_LAYER_MAP = {
     "attention.output.dense": "attn_out",
     "attention.output.LayerNorm": "attn_ln",
@@ -175,7 +259,7 @@ _HF_LAYER_MAP = {
 
 
 def from_hf_state_dict(sd: dict, num_layers: int) -> dict:
-    """HF ``BertForSequenceClassification`` state dict -> this model's."""
+    """HF ``BertForSequenceClassification`` / ``BertForPreTraining`` state dict -> this model's."""
     out = {}
     for k, v in sd.items():
         if k.startswith("bert.embeddings.") and "position_ids" not in k and "token_type_ids" not in k:
@@ -184,6 +268,11 @@ def from_hf_state_dict(sd: dict, num_layers: int) -> dict:
             out[k.replace("bert.pooler.dense.", "bert.pooler.")] = v
         elif k.startswith("classifier."):
             out[k] = v
+        elif k in _HF_HEAD_MAP:
+            out[_HF_HEAD_MAP[k]] = v
+        elif k in _HF_TIED:
+            if _HF_TIED[k] in sd and not torch.equal(v, sd[_HF_TIED[k]]):
+                raise ValueError(f"{k} is not tied to {_HF_TIED[k]}: this model shares the two")
     for i in range(num_layers):
         p = f"bert.encoder.layer.{i}."
         for t in ("weight", "bias"):
@@ -201,6 +290,13 @@ def to_hf_state_dict(sd: dict, num_layers: int) -> dict:
             out[k] = v
         elif k.startswith("bert.pooler."):
             out[k.replace("bert.pooler.", "bert.pooler.dense.")] = v
+    ours_to_hf = {v: k for k, v in _HF_HEAD_MAP.items()}
+    for k, v in sd.items():
+        if k in ours_to_hf:
+            out[ours_to_hf[k]] = v
+    if "mlm_bias" in sd:
+        out["cls.predictions.decoder.weight"] = sd["bert.embeddings.word_embeddings.weight"]
+        out["cls.predictions.decoder.bias"] = sd["mlm_bias"]
     for i in range(num_layers):
         p = f"bert.encoder.layer.{i}."
         for t in ("weight", "bias"):

@@ -6,18 +6,33 @@ for ORT, ``:174-178`` for PyTorch).
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 import torch.nn.functional as F
 
 from . import _lib
 
 
-def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    """Mean softmax cross-entropy, fp32 math, returns an fp32 scalar."""
-    if _lib.use_native(logits):
-        from . import _native_loss
-        return _native_loss.cross_entropy(logits, labels)
-    return F.cross_entropy(logits.float(), labels)
+def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, ignore_index: Optional[int] = None) -> torch.Tensor:
+    """Mean softmax cross-entropy, fp32 math, returns an fp32 scalar.
+
+    ``ignore_index``: rows whose label equals it take no part (the mean is over the other rows).
+    The one deliberate difference from ``F.cross_entropy``: when EVERY row is ignored the loss is 0
+    with a zero gradient, not NaN -- a NaN here would go straight into the fp32 master weights.
+    ``None`` (default) is the path without ignored targets, unchanged."""
+    if ignore_index is None:
+        if _lib.use_native(logits):
+            from . import _native_loss
+            return _native_loss.cross_entropy(logits, labels)
+        return F.cross_entropy(logits.float(), labels)
+    if _lib.use_native(logits) and logits.dim() == 2 and logits.dtype in (torch.bfloat16, torch.float32) \
+            and logits.numel() > 0:
+        from . import _native_mlm
+        return _native_mlm.cross_entropy_ignore(logits, labels, ignore_index)
+    x = logits if logits.dtype == torch.float64 else logits.float()
+    total = F.cross_entropy(x, labels, ignore_index=ignore_index, reduction="sum")
+    return total / (labels != ignore_index).sum().clamp(min=1)
 
 
 def softmax_topk(logits: torch.Tensor, k: int = 5):

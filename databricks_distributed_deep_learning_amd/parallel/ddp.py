@@ -329,6 +329,12 @@ class DataParallel(nn.Module):
         # parameter (dgrad before wgrad; BN / LN read gamma before reporting it).  With the
         # eager optimizer on, the bucket's update runs on a side stream from that point
         # and rewrites the weight.
+        # A parameter with TWO native producers in one backward (BERT pretraining: the decoder
+        # of the fused vocabulary head is the word-embedding table) is reported by the LAST of
+        # them only: the head adds its share to the slot and stays silent
+        # (``ops.linear_cross_entropy(defer_weight_ready=True)``), the embedding backward reports.
+        # The bucket then launches after both shares, one arrival is counted per pass, and the
+        # eager optimizer never sees a second report.
         def hook(_p, native: bool = False):
             # a native backward reports through grad_ready (native=True) and autograd's
             # post-accumulate hook then fires for the same parameter (its returned gradient

@@ -25,7 +25,7 @@ import torch
 from .. import ops
 from ..config import TrainConfig, apply_overrides
 from ..data import SyntheticImageNet, SyntheticTokens
-from ..models import build_model, cast_params, convert_sync_batchnorm, count_params
+from ..models import BertForPreTraining, build_model, cast_params, convert_sync_batchnorm, count_params
 from ..optim import LRSchedule, ParamArena, build_optimizer
 from ..parallel import dist as ddist
 from ..parallel.ddp import DataParallel
@@ -153,7 +153,8 @@ class Trainer:
         mc = getattr(self.model, "config", None)
         vocab = min(c.vocab_size, getattr(mc, "vocab_size", c.vocab_size))
         return SyntheticTokens(c.batch_size, c.seq_len, vocab, c.num_classes, self.device,
-                               rank=self.rank, seed=c.seed, pool=c.synthetic_pool, pad_fraction=c.pad_fraction)
+                               rank=self.rank, seed=c.seed, pool=c.synthetic_pool, pad_fraction=c.pad_fraction,
+                               mlm_predictions=c.mlm_predictions)
 
     def _auto_batch(self) -> int:
         from ..utils.memory import fit_batch_size
@@ -175,6 +176,12 @@ class Trainer:
         if self.task == "cv":
             x, y = batch
             return ops.cross_entropy(self.model(x), y)
+        if isinstance(self.model, BertForPreTraining):
+            if "masked_lm_labels" not in batch:
+                raise ValueError(f"{self.cfg.model} trains on masked-LM targets: set mlm_predictions > 0")
+            loss, _ = self.model(batch["input_ids"], batch.get("attention_mask"), None, batch["masked_lm_positions"],
+                                 batch["masked_lm_labels"], batch["next_sentence_label"])
+            return loss
         loss, _ = self.model(batch["input_ids"], batch.get("attention_mask"), None, batch["labels"])
         return loss
 
