@@ -58,12 +58,13 @@ def needs(src, obj, hdr_mtime):
 # 260), the skinny GEMMs.  gemm_big.hip's 8-wave kernels compile identically either way.
 _VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 EXTRA = {"gemm_big.hip": _VGPR_FORM, "conv3x3.hip": _VGPR_FORM, "skinny_gemm.hip": _VGPR_FORM,
-         "stream_gemm.hip": _VGPR_FORM, "gemm_duo.hip": _VGPR_FORM}
+         "stream_gemm.hip": _VGPR_FORM, "gemm_duo.hip": _VGPR_FORM, "conv3_bwd.hip": _VGPR_FORM}
 
 
 # Sources whose code decides which GEMM kernel runs fastest for a shape: their hash keys the committed
 # kernel plan table (ops/gemm_plans.json) -- a plan tuned against other GEMM kernels is not used.
-GEMM_SOURCES = ["gemm.hip", "gemm_big.hip", "gemm_duo.hip", "skinny_gemm.hip", "stream_gemm.hip", "conv3x3.hip"]
+GEMM_SOURCES = ["gemm.hip", "gemm_big.hip", "gemm_duo.hip", "skinny_gemm.hip", "stream_gemm.hip", "conv3x3.hip",
+                "conv3_bwd.hip"]
 
 
 def gemm_src_hash() -> str:

@@ -103,6 +103,35 @@ template <typename T> __device__ __forceinline__ T from_f(float x);
 template <> __device__ __forceinline__ float from_f<float>(float x) { return x; }
 template <> __device__ __forceinline__ bf16_t from_f<bf16_t>(float x) { return f2bf(x); }
 
+// ---------------------------------------------------------------- BatchNorm backward apply
+// dx = k1 (dz - mean(dz) - xhat mean(dz xhat)) folded into dx = A dz + B x + D per channel, from the
+// finalize's coef = [k1 | mean(dz) | mean(dz xhat)].  ONE spelling, with the fused multiply-adds
+// explicit, shared by the apply pass (norm.hip bn_bwd_apply_rows_k) and the kernel that forms dx in
+// LDS instead (conv3_bwd.hip): both give the same bits whatever the compiler would contract.
+__device__ __forceinline__ void bn_bwd_apply_coefs8(const float* mean, const float* invstd, const float* coef, int C,
+                                                    int c0, float* A, float* B, float* D) {
+    float mu[8], is[8], k1[8], mb[8], mg[8];
+    load8(mean + c0, mu);
+    load8(invstd + c0, is);
+    load8(coef + c0, k1);
+    load8(coef + C + c0, mb);
+    load8(coef + 2 * C + c0, mg);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        A[j] = k1[j];
+        B[j] = (-k1[j] * is[j]) * mg[j];
+        D[j] = k1[j] * __builtin_fmaf(mu[j] * is[j], mg[j], -mb[j]);
+    }
+}
+__device__ __forceinline__ float bn_bwd_apply1(float A, float dz, float B, float x, float D) {
+    return __builtin_fmaf(A, dz, B * x) + D;
+}
+
+// dW (+)= the sum of G bf16 partials of an M x N weight gradient (stream_gemm.hip wgrad_reduce_k), C
+// bf16 or fp32 (c_f32): the one reduce of stream_wgrad_k and conv3_bwd_k.  Returns the HIP error.
+int ddl_wgrad_reduce(const void* part, int G, int M, int N, void* C, long ldc, int accumulate, int c_f32,
+                     hipStream_t st);
+
 // ---------------------------------------------------------------- reductions
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -420,28 +420,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rows_k(const T* __restrict__
     const int tpr = C / 8, rpb = 256 / tpr;
     const int cg = threadIdx.x % tpr, rr = threadIdx.x / tpr;
     float A[8], B[8], D[8];
-    {
-        float mu[8], is[8], k1[8], mb[8], mg[8];
-        load8(mean + cg * 8, mu);
-        load8(invstd + cg * 8, is);
-        load8(coef + cg * 8, k1);
-        load8(coef + C + cg * 8, mb);
-        load8(coef + 2 * C + cg * 8, mg);
-        // dx = k1 * (dz - mb - (x - mu) * is * mg)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            A[j] = k1[j];
-            B[j] = -k1[j] * is[j] * mg[j];
-            D[j] = k1[j] * (mu[j] * is[j] * mg[j] - mb[j]);
-        }
-    }
+    // dx = k1 * (dz - mb - (x - mu) * is * mg) (ddl_common.h: the spelling conv3_bwd.hip shares)
+    bn_bwd_apply_coefs8(mean, invstd, coef, C, cg * 8, A, B, D);
     const long rs = (long)gridDim.x * rpb;
     auto one = [&](const float* g, const float* xv, uint32_t bits, long row) {
         float o[8], dz[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             dz[j] = ((bits >> j) & 1u) ? g[j] : 0.f;
-            o[j] = A[j] * dz[j] + B[j] * xv[j] + D[j];
+            o[j] = bn_bwd_apply1(A[j], dz[j], B[j], xv[j], D[j]);
         }
         store8(dx + row * C + cg * 8, o);
         if (DRES) store8(dres + row * C + cg * 8, dz);
@@ -1735,6 +1722,27 @@ DDL_API int ddl_bn_bwd_finish(int dtype, const void* dy, const void* mask, const
     DDL_RETURN_LAUNCH();
 }
 
+// backward coefficients (+ dgamma / dbeta) from the [sum dz | sum dz*xhat] partial rows a dgrad GEMM
+// wrote: the finalize ddl_bn_bwd_from_partials runs, on its own.  0, or -2: ws too small
+static int bn_bwd_coef_partials(const float* part, int nrows, float* ws, long ws_elems, const float* invstd,
+                                const bf16_t* gamma, long M, int C, bf16_t* dgamma, bf16_t* dbeta, float* coef,
+                                int acc_params, hipStream_t st) {
+    if (merged_finalize(nrows, C) && (fin_slices(nrows) == 1 || (ws && ws_elems >= (long)fin_slices(nrows) * 2 * C))) {
+        bwd_finalize<bf16_t>(part, nrows, fin_slices(nrows) == 1 ? nullptr : ws, C, M, gamma, invstd, dgamma, dbeta,
+                             coef, acc_params, st);
+        return 0;
+    }
+    const long need = ddl_bn_partials_ws(nrows, C);
+    if (need > 0 && (!ws || ws_elems < need)) return -2;
+    if (need > 0) {
+        bwd_finalize<bf16_t>(part, nrows, ws, C, M, gamma, invstd, dgamma, dbeta, coef, acc_params, st);
+        return 0;
+    }
+    bn_bwd_finalize_k<bf16_t><<<(C + 63) / 64, 1024, 0, st>>>(part, nrows, C, M, gamma, invstd, dgamma, dbeta, coef,
+                                                              acc_params, nullptr);
+    return 0;
+}
+
 // backward from [sum dz | sum dz*xhat] partial rows written by the dgrad GEMM that
 // produced dz (ACT_BNB epilogue: dz already carries the ReLU mask); ws: ceil(nrows/32) * 2C
 // floats for the 32:1 collapse (may be null when nrows <= 256)
@@ -1743,23 +1751,32 @@ DDL_API int ddl_bn_bwd_from_partials(int dtype, const float* part, int nrows, fl
                                      const void* gamma, long M, int C, void* dgamma, void* dbeta, float* coef, void* dx,
                                      void* dres, int acc_params, hipStream_t st) {
     if (!rows_ok(C) || dtype != 1) return -1;
-    if (merged_finalize(nrows, C) && (fin_slices(nrows) == 1 || (ws && ws_elems >= (long)fin_slices(nrows) * 2 * C))) {
-        bwd_finalize<bf16_t>(part, nrows, fin_slices(nrows) == 1 ? nullptr : ws, C, M, (const bf16_t*)gamma, invstd,
-                             (bf16_t*)dgamma, (bf16_t*)dbeta, coef, acc_params, st);
-        bn_bwd_apply_only((const bf16_t*)dz, nullptr, (const bf16_t*)x, mean, invstd, M, C, 0, coef, (bf16_t*)dx,
-                          (bf16_t*)dres, st);
-        DDL_RETURN_LAUNCH();
-    }
-    const long need = ddl_bn_partials_ws(nrows, C);
-    if (need > 0 && (!ws || ws_elems < need)) return -2;
-    if (need > 0) {
-        bwd_finalize<bf16_t>(part, nrows, ws, C, M, (const bf16_t*)gamma, invstd, (bf16_t*)dgamma, (bf16_t*)dbeta, coef,
-                             acc_params, st);
-        bn_bwd_apply_only((const bf16_t*)dz, nullptr, (const bf16_t*)x, mean, invstd, M, C, 0, coef, (bf16_t*)dx,
-                          (bf16_t*)dres, st);
-        DDL_RETURN_LAUNCH();
-    }
-    bn_bwd_finish_t((const bf16_t*)dz, nullptr, (const bf16_t*)x, mean, invstd, (const bf16_t*)gamma, M, M, C, 0, part,
-                    nrows, (bf16_t*)dgamma, (bf16_t*)dbeta, coef, (bf16_t*)dx, (bf16_t*)dres, acc_params, st);
+    const int rc = bn_bwd_coef_partials(part, nrows, ws, ws_elems, invstd, (const bf16_t*)gamma, M, C, (bf16_t*)dgamma,
+                                        (bf16_t*)dbeta, coef, acc_params, st);
+    if (rc != 0) return rc;
+    bn_bwd_apply_only((const bf16_t*)dz, nullptr, (const bf16_t*)x, mean, invstd, M, C, 0, coef, (bf16_t*)dx,
+                      (bf16_t*)dres, st);
+    DDL_RETURN_LAUNCH();
+}
+
+// the two halves of ddl_bn_bwd_from_partials on their own, for a consumer that folds the apply into
+// its own pass (conv3_bwd.hip): the finalize (coef, dgamma, dbeta) ...
+DDL_API int ddl_bn_bwd_coef_from_partials(int dtype, const float* part, int nrows, float* ws, long ws_elems,
+                                          const float* invstd, const void* gamma, long M, int C, void* dgamma,
+                                          void* dbeta, float* coef, int acc_params, hipStream_t st) {
+    if (!rows_ok(C) || dtype != 1) return -1;
+    const int rc = bn_bwd_coef_partials(part, nrows, ws, ws_elems, invstd, (const bf16_t*)gamma, M, C, (bf16_t*)dgamma,
+                                        (bf16_t*)dbeta, coef, acc_params, st);
+    if (rc != 0) return rc;
+    DDL_RETURN_LAUNCH();
+}
+
+// ... and the apply dx = k1 (dz - mean(dz) - xhat mean(dz xhat)) from those coefficients (dz
+// already carries the ReLU mask), for when that consumer cannot fold it after all
+DDL_API int ddl_bn_bwd_apply_coef(int dtype, const void* dz, const void* x, const float* mean, const float* invstd,
+                                  const float* coef, long M, int C, void* dx, hipStream_t st) {
+    if (!rows_ok(C) || dtype != 1) return -1;
+    bn_bwd_apply_only((const bf16_t*)dz, nullptr, (const bf16_t*)x, mean, invstd, M, C, 0, coef, (bf16_t*)dx,
+                      (bf16_t*)nullptr, st);
     DDL_RETURN_LAUNCH();
 }

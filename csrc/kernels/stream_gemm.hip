@@ -569,8 +569,9 @@ __global__ __launch_bounds__(512, 1) void stream_wgrad_k(WgParams p) {
 }
 
 // C[m][n] (+)= sum over the G bf16 partials: 64 output quads x 4 partial lanes per workgroup
+template <typename TO>
 __global__ __launch_bounds__(256) void wgrad_reduce_k(const bf16_t* __restrict__ part, int G, int M, int N,
-                                                      bf16_t* __restrict__ C, long ldc, int accumulate) {
+                                                      TO* __restrict__ C, long ldc, int accumulate) {
     __shared__ f32x4 red[256];
     const int quad = blockIdx.x * 64 + (threadIdx.x & 63), gl = threadIdx.x >> 6;
     const int nq = M * N / 4;
@@ -603,7 +604,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_k(const bf16_t* __restrict__
     if (gl != 0 || quad >= nq) return;
     const f32x4 t = red[threadIdx.x] + red[threadIdx.x + 64] + red[threadIdx.x + 128] + red[threadIdx.x + 192];
     const int m = quad * 4 / N, n = quad * 4 - m * N;
-    bf16_t* dst = C + (long)m * ldc + n;
+    TO* dst = C + (long)m * ldc + n;
     float o[4] = {t[0], t[1], t[2], t[3]};
     if (accumulate) {
         float a[4];
@@ -618,12 +619,22 @@ template <int M, int N>
 int launch_wgrad(const WgParams& p0, int G, bf16_t* C, long ldc, int accumulate, hipStream_t st) {
     WgParams p = p0;
     hipLaunchKernelGGL((stream_wgrad_k<M, N>), dim3(G), dim3(512), 0, st, p);
-    hipLaunchKernelGGL(wgrad_reduce_k, dim3((M * N / 4 + 63) / 64), dim3(256), 0, st, (const bf16_t*)p.part, G, M, N, C,
-                       ldc, accumulate);
-    return (int)hipGetLastError();
+    return ddl_wgrad_reduce(p.part, G, M, N, C, ldc, accumulate, 0, st);
 }
 
 }  // namespace
+
+int ddl_wgrad_reduce(const void* part, int G, int M, int N, void* C, long ldc, int accumulate, int c_f32,
+                     hipStream_t st) {
+    const dim3 grid((M * N / 4 + 63) / 64);
+    if (c_f32)
+        hipLaunchKernelGGL(wgrad_reduce_k<float>, grid, dim3(256), 0, st, (const bf16_t*)part, G, M, N, (float*)C, ldc,
+                           accumulate);
+    else
+        hipLaunchKernelGGL(wgrad_reduce_k<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)part, G, M, N, (bf16_t*)C,
+                           ldc, accumulate);
+    return (int)hipGetLastError();
+}
 
 // TN weight gradient C[M, N] (+)= A^T B, A = [K][lda], B = [K][ldb] bf16 (lda, ldb % 8 == 0, 16-byte
 // aligned), C bf16 (ldc % 4 == 0), M, N in {64, 128, 256, 512} with M * N <= 65536.  workspace:

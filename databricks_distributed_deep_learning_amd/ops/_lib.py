@@ -138,6 +138,8 @@ _SIGS = {
     "ddl_bn_relu_maxpool": [I, P, P, P, P, P, P, I, I, I, I, I, I, P],
     "ddl_bn_bwd_pool_nblk": [],
     "ddl_bn_bwd_pool": [I, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, I, P],
+    "ddl_bn_bwd_coef_from_partials": [I, P, I, P, L, P, P, L, I, P, P, P, I, P],
+    "ddl_bn_bwd_apply_coef": [I, P, P, P, P, P, L, I, P, P],
     "ddl_bn_fwd_from_partials": [I, P, I, L, I, P, P, P, P, F, F, P, P, P, P, P, L],
     "ddl_conv_w_dgrad": [P, P, I, I, I, I, I, I, P, P, P],
     "ddl_conv_w_dgrad_batch": [P, P, I, P],
@@ -166,6 +168,9 @@ _SIGS = {
     "ddl_skinny_gemm": [P, P, P, L, I, I, P, P, P, P, P, P, I, P],
     "ddl_stream_gemm": [P, P, P, L, I, I, P, P, P, P, P, P, I, P],
     "ddl_stream_wgrad_ws": [I, I],
+    # conv3_bwd.hip
+    "ddl_conv3_bwd_grid": [L, I],
+    "ddl_conv3_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, P, I, I, L, I, I, I, P],
     "ddl_bn_bwd": [I, P, P, P, P, P, P, L, I, I, P, P, P, P, P, P, I, P],
     "ddl_ln_supported": [I],
     "ddl_ln_fwd": [I, P, P, L, P, P, P, P, P, L, I, F, U64, F, P],

@@ -494,12 +494,75 @@ def _wgrad(dy, x, w_shape, stride, pad, out=None):
     return dw
 
 
+def _conv3_fold_ok(x, w, stride, pad) -> bool:
+    """Convolutions whose backward the fused conv3 / bn3 kernel covers (csrc/kernels/conv3_bwd.hip):
+    1x1, stride 1, (C_out, C_in) in bridge.CONV3_SHAPES, bf16, contiguous, on the GPU.  Stage 1's
+    downsample conv has the same shape and gets a hint too; the dual BatchNorm apply never keeps it
+    for its second input, so nothing is ever parked there and that conv's backward is unchanged."""
+    from . import bridge as B
+    K, R, S, C = w.shape
+    return (B.CONV3_FUSED and R == 1 and S == 1 and stride == 1 and pad == 0 and (K, C) in B.CONV3_SHAPES
+            and x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.is_contiguous()
+            and w.is_contiguous() and x.numel() // C * K * 2 < 2 ** 31)
+
+
+def _conv3_bwd_fused(parked, x, w, bnb, param, sink):
+    """dx (the BatchNorm-backward sums of ``bnb`` from its epilogue) and dW (into ``sink`` when
+    given) of a 1x1 convolution whose output gradient is the parked BatchNorm apply
+    (ops.bridge.Conv3Fold): one pass over dz, the BN input, x and the BN-backward operand.
+    Returns (dx, dw) -- dw None with a sink -- or None when not covered (nothing launched)."""
+    dz, x3, mean3, istd3, coef = parked
+    N, H, W_, C = x.shape
+    K = w.shape[0]
+    M = N * H * W_
+    if (bnb is None or not _BN_BWD_EPI or tuple(bnb.x.shape) != tuple(x.shape) or not bnb.x.is_contiguous()
+            or bnb.x.dtype != torch.bfloat16 or x3.numel() != M * K or dz.numel() != M * K
+            or not dz.is_contiguous() or not x3.is_contiguous()
+            or (bnb.mask is not None and bnb.mask.numel() * 8 < M * C)):
+        return None
+    if sink is not None and (not sink.is_contiguous() or sink.dtype not in (torch.bfloat16, torch.float32)):
+        return None
+    wt = _w_dgrad(w, [0], [0], param).view(C, K)
+    dx = torch.empty(N, H, W_, C, dtype=x.dtype, device=x.device)
+    dw = sink if sink is not None else torch.empty(K, 1, 1, C, dtype=x.dtype, device=x.device)
+    G = _lib.fn("ddl_conv3_bwd_grid")(M, 0)
+    part = torch.empty(max(stats_rows_max(M), 1024) * 2 * C + 64 * C, dtype=torch.float32, device=x.device)
+    wpart = torch.empty(G * K * C, dtype=torch.bfloat16, device=x.device)
+    rc = _lib.fn("ddl_conv3_bwd")(dz.data_ptr(), x3.data_ptr(), mean3.data_ptr(), istd3.data_ptr(), coef.data_ptr(),
+                                  x.data_ptr(), bnb.x.data_ptr(), _lib.p(bnb.mask), bnb.mean.data_ptr(),
+                                  bnb.istd.data_ptr(), wt.data_ptr(), dx.data_ptr(), part.data_ptr(),
+                                  wpart.data_ptr(), wpart.numel(), dw.data_ptr(), int(dw.dtype == torch.float32),
+                                  int(sink is not None), M, K, C, 0, _lib.stream())
+    if rc == -1:
+        return None
+    if rc < 0:
+        raise RuntimeError(f"ddl_conv3_bwd failed: {rc}")
+    bnb.set(dx, part, rc)
+    return dx, (None if sink is not None else dw)
+
+
+def _conv3_materialise(parked, dy):
+    """The gradient the ordinary dgrad / wgrad need when a BatchNorm parked its apply pass
+    (ops.bridge.Conv3Fold) but the fused kernel does not run: dx3 by the apply kernel, and the
+    received gradient corrected by - dz + dx3 when it is not dz itself (a second consumer, a hook)."""
+    from .bridge import Conv3Fold
+    dz, x3, mean3, istd3, coef = parked
+    C = x3.shape[-1]
+    dx3 = torch.empty_like(x3)
+    _lib.call("ddl_bn_bwd_apply_coef", 1, dz.data_ptr(), x3.data_ptr(), mean3.data_ptr(), istd3.data_ptr(),
+              coef.data_ptr(), x3.numel() // C, C, dx3.data_ptr())
+    if Conv3Fold.is_parked(parked, dy):
+        return dx3
+    return (dy - dz.view_as(dy)) + dx3.view_as(dy)
+
+
 class _Conv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, stride, pad, bridge=None, stats=None, grad_to=None):
         ctx.w_param = w
         ctx.bridge = bridge
         ctx.grad_to = grad_to
+        ctx.c3 = None
         # input is a training BatchNorm's output: its backward reduction can ride this dgrad
         # (not when the gradient is offered to a sibling conv, which adds unmasked terms)
         ctx.bnb = getattr(x, "_ddl_bnb", None) if grad_to is None else None
@@ -507,13 +570,34 @@ class _Conv(torch.autograd.Function):
         w = w.contiguous()
         ctx.stride, ctx.pad = stride, pad
         ctx.save_for_backward(x, w)
-        return _fwd(x, w, stride, pad, stats=stats)
+        y = _fwd(x, w, stride, pad, stats=stats)
+        if _conv3_fold_ok(x, w, stride, pad) and y.is_contiguous():
+            # the BatchNorm that consumes y may leave its backward apply pass to this conv's backward
+            from .bridge import Conv3Fold
+            ctx.c3 = y._ddl_c3 = Conv3Fold()
+        return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
         dy = dy.contiguous()
         dx = dw = None
+        parked = ctx.c3.take() if ctx.c3 is not None else None
+        if parked is not None:
+            from .bridge import Conv3Fold
+            if (Conv3Fold.is_parked(parked, dy) and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
+                    and ctx.bridge is None and ctx.grad_to is None):
+                sink = grad_sink(ctx.w_param)
+                if sink is not None and sink.shape != w.shape:
+                    sink = None
+                out = _conv3_bwd_fused(parked, x, w, ctx.bnb, ctx.w_param, sink)
+                if out is not None:
+                    ctx.bnb = None
+                    if sink is not None:
+                        grad_ready(ctx.w_param)
+                    return out[0], out[1], None, None, None, None, None
+            dy = _conv3_materialise(parked, dy)
+        del parked
         fork = _lib.fork_event() if ctx.needs_input_grad[1] else None   # wgrad may start here
         if ctx.needs_input_grad[0]:
             res = ctx.bridge.take() if ctx.bridge is not None else None

@@ -74,6 +74,7 @@ class _BatchNormTrain(torch.autograd.Function):
                 pre=None, group=None):
         ctx.bridge = bridge
         ctx.group = group
+        ctx.c3 = _conv3_hint(x) if group is None else None
         x = x.contiguous()
         C = x.shape[-1]
         M = x.numel() // C
@@ -127,6 +128,15 @@ class _BatchNormTrain(torch.autograd.Function):
         return dx, dgamma, dbeta, None, None, None, None, None, dres, None, None, None
 
 
+def _conv3_hint(x):
+    """The ops.bridge.Conv3Fold the producing convolution left on ``x`` (None: no fold): kept only
+    for the very tensor the BatchNorm will save, and only when its gradient is asked for."""
+    hint = getattr(x, "_ddl_c3", None)
+    if hint is None or not x.is_contiguous() or x.dtype != torch.bfloat16 or not x.requires_grad:
+        return None
+    return hint
+
+
 def _bn_backward(ctx, dy, x, mask, weight, stats):
     """Training BatchNorm backward -> (dx, dgamma, dbeta, dres).  ``ctx`` carries bnb (the
     dgrad-epilogue hint), group, has_res, relu, params, bridge and m_total (SyncBN)."""
@@ -138,7 +148,6 @@ def _bn_backward(ctx, dy, x, mask, weight, stats):
     # partial rows + room for their 32:1 collapse (see norm.hip collapse_partials)
     part = torch.empty((nblk + -(-nblk // 32)) * 2 * C, **f32)
     coef = torch.empty(3 * C, **f32)
-    dx = torch.empty_like(x)
     sg, sb = grad_sink(ctx.params[0]), grad_sink(ctx.params[1])
     direct = sg is not None and sb is not None
     if direct:
@@ -148,6 +157,10 @@ def _bn_backward(ctx, dy, x, mask, weight, stats):
         dbeta = torch.empty_like(weight) if weight is not None else None
     given = ctx.bnb.take_for(dy) if ctx.bnb is not None else None
     ctx.bnb = None
+    c3 = getattr(ctx, "c3", None)
+    # the producing 1x1 convolution forms dx inside its own backward pass (ops/bridge.py Conv3Fold)
+    fold = c3 is not None and given is not None and ctx.group is None and weight is not None
+    dx = None if fold else torch.empty_like(x)
     dres = torch.empty_like(x) if ctx.has_res and (given is None or ctx.group is not None) else None
     if given is not None:
         # dy is dz (ReLU mask applied) and [sum dz | sum dz*xhat] came from the dgrad epilogue
@@ -159,6 +172,14 @@ def _bn_backward(ctx, dy, x, mask, weight, stats):
             _group_sum(row, ctx.group)
             call("ddl_bn_bwd_finish", dcode(x), p(dy), None, p(x), p(stats[0]), p(stats[1]), p(weight), M,
                  ctx.m_total, C, 0, p(row), p(local), p(dgamma), p(dbeta), p(coef), p(dx), p(dres), int(direct))
+        elif fold:
+            ws = gpart[nrows * 2 * C:]
+            call("ddl_bn_bwd_coef_from_partials", dcode(x), p(gpart), nrows, p(ws), ws.numel(), p(stats[1]),
+                 p(weight), M, C, p(dgamma), p(dbeta), p(coef), int(direct))
+            c3.park(dy, x, stats[0], stats[1], coef)
+            dx = dy
+            if ctx.has_res:
+                dres = dy
         else:
             ws = gpart[nrows * 2 * C:]
             # the residual gradient IS dz (mask applied, no affine): hand on the dgrad's
@@ -202,6 +223,7 @@ class _BatchNormAddBNTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, x2, weight2, bias2, running_mean2,
                 running_var2, momentum2, eps2, pre=None, pre2=None):
+        ctx.c3 = _conv3_hint(x)
         x, x2 = x.contiguous(), x2.contiguous()
         C = x.shape[-1]
         f32 = dict(dtype=torch.float32, device=x.device)

@@ -21,9 +21,16 @@ autograd itself.  Either execution order sums both gradients exactly once.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
+
+# conv3 -> bn3 backward in one streaming pass (csrc/kernels/conv3_bwd.hip, ``Conv3Fold``);
+# DDL_CONV3_BWD_FUSED=0 keeps the apply pass, the dgrad and the wgrad as three kernels
+CONV3_FUSED = os.environ.get("DDL_CONV3_BWD_FUSED", "1") != "0"
+# (C_out, C_in) of the 1x1 convolutions the fused kernel covers (ResNet stage 1)
+CONV3_SHAPES = ((256, 64),)
 
 
 class GradBridge:
@@ -121,3 +128,45 @@ class BNBackward:
         if dz is None or dz.data_ptr() != g.data_ptr() or dz.numel() != g.numel():
             return None
         return part, nrows
+
+
+class Conv3Fold:
+    """Lets a BatchNorm leave its backward apply pass to the 1x1 convolution that produced its
+    input (backward-time side channel, csrc/kernels/conv3_bwd.hip).
+
+    The convolution puts one on its output in training when the fused kernel covers its shape; the
+    BatchNorm keeps the one it finds on its input.  In backward a BatchNorm whose incoming gradient
+    already is dz (its reduction came from a dgrad epilogue, ``BNBackward``) runs only its finalize,
+    parks ``(dz, x, mean, istd, coef)`` here and returns dz itself as its input gradient: dx =
+    coef-affine(dz, x) is then formed inside the convolution's fused dgrad + wgrad pass.  The
+    convolution takes what is parked whatever path it runs: if the gradient it received is not that
+    very dz (another consumer, a hook), ``materialise`` gives the dx the apply pass would have
+    written and the received gradient is corrected by ``- dz + dx``.  Parking keeps a reference to
+    dz, which also stops autograd from accumulating into it in place.
+
+    Two consequences of handing dz through autograd in dx's place: a tensor hook or ``retain_grad``
+    on the convolution's output observes dz, not the true gradient dx (only a hook that returns a new
+    tensor reaches the correction path, which then treats its change as additive); and when autograd
+    prunes the convolution's node (``autograd.grad`` for inputs that do not need it) nobody takes
+    the parked tensors, which then live until the graph is freed."""
+    __slots__ = ("parked",)
+
+    def __init__(self):
+        self.parked = None
+
+    def park(self, dz: torch.Tensor, x: torch.Tensor, mean: torch.Tensor, istd: torch.Tensor,
+             coef: torch.Tensor) -> None:
+        if self.parked is not None:
+            raise RuntimeError("Conv3Fold: a gradient is already parked (hint reused within one backward?)")
+        self.parked = (dz, x, mean, istd, coef)
+
+    def take(self):
+        """What the BatchNorm parked (None: it ran its own apply pass); nothing stays parked."""
+        parked, self.parked = self.parked, None
+        return parked
+
+    @staticmethod
+    def is_parked(parked, g: torch.Tensor) -> bool:
+        """Is ``g`` the very dz that was parked (same storage pointer and size)?"""
+        dz = parked[0]
+        return dz.data_ptr() == g.data_ptr() and dz.numel() == g.numel() and dz.dtype == g.dtype
