@@ -57,12 +57,16 @@ __global__ __launch_bounds__(OPT_NT) void sgd_k(const G* __restrict__ grad, floa
     }
 }
 
+// omb1 / omb2 = 1 - beta1 / 1 - beta2, formed by the caller in double and rounded once (as
+// torch.optim does).  1.f - b2 here would carry the rounding of beta2 to fp32 (up to 2^-25
+// absolute) into a factor of size 1e-3: v off by 1.3e-5 relative for beta2 = 0.999, ~130x the
+// error of a correct fp32 step.
 template <typename G, typename P>
 __global__ __launch_bounds__(OPT_NT) void adamw_k(const G* __restrict__ grad, float* __restrict__ master,
                                                    P* __restrict__ param, float* __restrict__ m_, float* __restrict__ v_,
                                                    const int4* __restrict__ table, const float* __restrict__ scale_p,
-                                                   float lr, float b1, float b2, float eps, float wd, float bc1,
-                                                   float bc2) {
+                                                   float lr, float b1, float b2, float omb1, float omb2, float eps,
+                                                   float wd, float bc1, float bc2) {
     const int4 e = table[blockIdx.x];
     const int len = e.y & 0x3fffffff;
     const float scale = scale_p[0];
@@ -79,8 +83,8 @@ __global__ __launch_bounds__(OPT_NT) void adamw_k(const G* __restrict__ grad, fl
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float gg = g[j] * scale;
-            m[j] = b1 * m[j] + (1.f - b1) * gg;
-            v[j] = b2 * v[j] + (1.f - b2) * gg * gg;
+            m[j] = b1 * m[j] + omb1 * gg;
+            v[j] = b2 * v[j] + omb2 * gg * gg;
             p[j] = p[j] * decay - step_size * m[j] / (sqrtf(v[j]) * inv_sqrt_bc2 + eps);
         }
         store8(master + i, p);
@@ -95,8 +99,8 @@ template <typename G>
 __global__ __launch_bounds__(OPT_NT) void lamb_phase1_k(const G* __restrict__ grad, const float* __restrict__ master,
                                                          float* __restrict__ m_, float* __restrict__ v_,
                                                          const int4* __restrict__ table, const float* __restrict__ scale_p,
-                                                         float b1, float b2, float eps, float wd, float bc1, float bc2,
-                                                         float* __restrict__ norms) {
+                                                         float b1, float b2, float omb1, float omb2, float eps, float wd,
+                                                         float bc1, float bc2, float* __restrict__ norms) {
     __shared__ float red[4];
     const int4 e = table[blockIdx.x];
     const int len = e.y & 0x3fffffff;
@@ -113,8 +117,8 @@ __global__ __launch_bounds__(OPT_NT) void lamb_phase1_k(const G* __restrict__ gr
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float gg = g[j] * scale;
-            m[j] = b1 * m[j] + (1.f - b1) * gg;
-            v[j] = b2 * v[j] + (1.f - b2) * gg * gg;
+            m[j] = b1 * m[j] + omb1 * gg;
+            v[j] = b2 * v[j] + omb2 * gg * gg;
             float u = (m[j] / bc1) / (sqrtf(v[j] / bc2) + eps);
             if (dec) u += wd * p[j];
             pn += p[j] * p[j];
@@ -188,10 +192,10 @@ DDL_API int ddl_sgd_step(int gdtype, const void* grad, float* master, int pdtype
 }
 
 DDL_API int ddl_adamw_step(int gdtype, const void* grad, float* master, int pdtype, void* param, float* m, float* v,
-                           const int* table, int nblk, const float* scale, float lr, float b1, float b2, float eps,
-                           float wd, float bc1, float bc2, hipStream_t st) {
+                           const int* table, int nblk, const float* scale, float lr, float b1, float b2, float omb1,
+                           float omb2, float eps, float wd, float bc1, float bc2, hipStream_t st) {
     const int4* t = (const int4*)table;
-#define ADAM_CALL(G, P) adamw_k<G, P><<<nblk, OPT_NT, 0, st>>>((const G*)grad, master, (P*)param, m, v, t, scale, lr, b1, b2, eps, wd, bc1, bc2)
+#define ADAM_CALL(G, P) adamw_k<G, P><<<nblk, OPT_NT, 0, st>>>((const G*)grad, master, (P*)param, m, v, t, scale, lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2)
     if (gdtype == 1) { if (pdtype == 1) ADAM_CALL(bf16_t, bf16_t); else ADAM_CALL(bf16_t, float); }
     else { if (pdtype == 1) ADAM_CALL(float, bf16_t); else ADAM_CALL(float, float); }
 #undef ADAM_CALL
@@ -200,15 +204,15 @@ DDL_API int ddl_adamw_step(int gdtype, const void* grad, float* master, int pdty
 
 // norms: fp32[2 * ntensors], zeroed by the caller before the call
 DDL_API int ddl_lamb_step(int gdtype, const void* grad, float* master, int pdtype, void* param, float* m, float* v,
-                          const int* table, int nblk, const float* scale, float lr, float b1, float b2, float eps,
-                          float wd, float bc1, float bc2, float* norms, hipStream_t st) {
+                          const int* table, int nblk, const float* scale, float lr, float b1, float b2, float omb1,
+                          float omb2, float eps, float wd, float bc1, float bc2, float* norms, hipStream_t st) {
     const int4* t = (const int4*)table;
     if (gdtype == 1)
-        lamb_phase1_k<bf16_t><<<nblk, OPT_NT, 0, st>>>((const bf16_t*)grad, master, m, v, t, scale, b1, b2, eps, wd, bc1,
-                                                       bc2, norms);
+        lamb_phase1_k<bf16_t><<<nblk, OPT_NT, 0, st>>>((const bf16_t*)grad, master, m, v, t, scale, b1, b2, omb1, omb2,
+                                                       eps, wd, bc1, bc2, norms);
     else
-        lamb_phase1_k<float><<<nblk, OPT_NT, 0, st>>>((const float*)grad, master, m, v, t, scale, b1, b2, eps, wd, bc1,
-                                                      bc2, norms);
+        lamb_phase1_k<float><<<nblk, OPT_NT, 0, st>>>((const float*)grad, master, m, v, t, scale, b1, b2, omb1, omb2,
+                                                      eps, wd, bc1, bc2, norms);
     if (pdtype == 1)
         lamb_phase2_k<bf16_t><<<nblk, OPT_NT, 0, st>>>(master, (bf16_t*)param, m, v, t, lr, eps, wd, bc1, bc2, norms);
     else
@@ -219,15 +223,15 @@ DDL_API int ddl_lamb_step(int gdtype, const void* grad, float* master, int pdtyp
 // LAMB as two launches, for the sharded optimizer: per-tensor norms of a rank's
 // slice are all-reduced between phase 1 (moments + partial norms) and phase 2
 DDL_API int ddl_lamb_phase1(int gdtype, const void* grad, float* master, float* m, float* v, const int* table,
-                            int nblk, const float* scale, float b1, float b2, float eps, float wd, float bc1, float bc2,
-                            float* norms, hipStream_t st) {
+                            int nblk, const float* scale, float b1, float b2, float omb1, float omb2, float eps, float wd,
+                            float bc1, float bc2, float* norms, hipStream_t st) {
     const int4* t = (const int4*)table;
     if (gdtype == 1)
-        lamb_phase1_k<bf16_t><<<nblk, OPT_NT, 0, st>>>((const bf16_t*)grad, master, m, v, t, scale, b1, b2, eps, wd, bc1,
-                                                       bc2, norms);
+        lamb_phase1_k<bf16_t><<<nblk, OPT_NT, 0, st>>>((const bf16_t*)grad, master, m, v, t, scale, b1, b2, omb1, omb2,
+                                                       eps, wd, bc1, bc2, norms);
     else
-        lamb_phase1_k<float><<<nblk, OPT_NT, 0, st>>>((const float*)grad, master, m, v, t, scale, b1, b2, eps, wd, bc1,
-                                                      bc2, norms);
+        lamb_phase1_k<float><<<nblk, OPT_NT, 0, st>>>((const float*)grad, master, m, v, t, scale, b1, b2, omb1, omb2,
+                                                      eps, wd, bc1, bc2, norms);
     DDL_RETURN_LAUNCH();
 }
 DDL_API int ddl_lamb_phase2(float* master, int pdtype, void* param, float* m, float* v, const int* table, int nblk,

@@ -81,8 +81,8 @@ def adamw(opt, grad, scale, rng=None):
     t = opt.step_count
     call("ddl_adamw_step", dcode(grad), p(grad), master, pdt, p(param), _state(opt.m, opt), _state(opt.v, opt),
          tab, nrow,
-         p(s), float(opt.lr), float(opt.b1), float(opt.b2), float(opt.eps), float(opt.weight_decay),
-         float(1 - opt.b1 ** t), float(1 - opt.b2 ** t))
+         p(s), float(opt.lr), float(opt.b1), float(opt.b2), float(1 - opt.b1), float(1 - opt.b2), float(opt.eps),
+         float(opt.weight_decay), float(1 - opt.b1 ** t), float(1 - opt.b2 ** t))
 
 
 def lamb(opt, grad, scale, rng=None):
@@ -102,15 +102,16 @@ def lamb(opt, grad, scale, rng=None):
     if opt.shard is None:
         tp, nrow = _rows(opt, rng)
         call("ddl_lamb_step", dcode(grad), p(grad), master, pdt, p(param), p(opt.m), p(opt.v), tp, nrow,
-             p(s), float(opt.lr), float(opt.b1), float(opt.b2), float(opt.eps), float(opt.weight_decay), float(bc1),
-             float(bc2), p(norms))
+             p(s), float(opt.lr), float(opt.b1), float(opt.b2), float(1 - opt.b1), float(1 - opt.b2), float(opt.eps),
+             float(opt.weight_decay), float(bc1), float(bc2), p(norms))
         return
     tab = _table(opt)
     # sharded: the per-tensor norms of every rank's pieces are summed between the phases
     from ..optim.flat import _sum_over_ranks
     m, v = _state(opt.m, opt), _state(opt.v, opt)
     call("ddl_lamb_phase1", dcode(grad), p(grad), master, m, v, p(tab), tab.shape[0], p(s), float(opt.b1),
-         float(opt.b2), float(opt.eps), float(opt.weight_decay), float(bc1), float(bc2), p(norms))
+         float(opt.b2), float(1 - opt.b1), float(1 - opt.b2), float(opt.eps), float(opt.weight_decay), float(bc1),
+         float(bc2), p(norms))
     _sum_over_ranks(norms)
     call("ddl_lamb_phase2", master, pdt, p(param), m, v, p(tab), tab.shape[0], float(opt.lr), float(opt.eps),
          float(opt.weight_decay), float(bc1), float(bc2), p(norms))
