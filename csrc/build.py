@@ -70,8 +70,9 @@ GEMM_SOURCES = ["gemm.hip", "gemm_big.hip", "gemm_duo.hip", "skinny_gemm.hip", "
 def gemm_src_hash() -> str:
     import hashlib
     h = hashlib.sha256()
-    for name in GEMM_SOURCES + ["../include/ddl_common.h"]:
-        path = os.path.normpath(os.path.join(CSRC, "kernels", name))
+    # (every shared header: an edit to any of them may change the kernels the plans were tuned against)
+    for path in [os.path.join(CSRC, "kernels", n) for n in GEMM_SOURCES] + \
+            sorted(glob.glob(os.path.join(CSRC, "include", "*.h"))):
         h.update(os.path.basename(path).encode())
         with open(path, "rb") as f:
             h.update(f.read())

@@ -21,6 +21,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define DDL_RETURN_LAUNCH() return (int)hipGetLastError()
 
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
+// the low / high bf16 of a packed pair
+__device__ __forceinline__ float lo_f(uint32_t u) { return __uint_as_float(u << 16); }
+__device__ __forceinline__ float hi_f(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
 
 // Round-to-nearest-even; NaN stays NaN.  hipcc lowers the __bf16 cast to
 // v_cvt_pk_bf16_f32 on gfx950.

@@ -22,7 +22,7 @@
 // stores the keep decisions as a bit mask (1 bit per score, dmask_word below); the
 // backward kernels read the bits instead of re-hashing every score (lane = key in
 // the dK/dV passes: one hash per score there cost ~2.4x the pass's MFMA time).
-#include "ddl_common.h"
+#include "ddl_lds.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -41,8 +41,6 @@ constexpr int TROWS_F = 16 * TWF, TROWS_B = 16 * TWB;
 constexpr int ROWB = 128;      // bytes per LDS row (64 bf16)
 constexpr int FS = 128;        // longest sequence of the one-workgroup-per-(b, h) kernels
 constexpr float LOG2E = 1.4426950408889634f;
-
-typedef __attribute__((address_space(3))) s16x4 lds_v4;
 
 // 2^x as the bare v_exp_f32: exp2f adds a denormal-range fix-up (ldexp, compare, select)
 // per call; softmax arguments are <= 0 and a result below 2^-126 may as well be 0
@@ -96,8 +94,8 @@ __device__ __forceinline__ bf16x8 frag_tr(const char* lds, int kb, int cbase) {
     const int half = DS ? ((p ^ ra) & 1) : (p & 1);
     const char* pa = lds + lds_off<TR, DS>(ra, col >> 3) + half * 8;
     const char* pb = lds + lds_off<TR, DS>(rb, col >> 3) + half * 8;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)pa);
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)pb);
+    s16x4 lo = lds_read_tr((lds_v4*)pa);
+    s16x4 hi = lds_read_tr((lds_v4*)pb);
     typedef short s16x8 __attribute__((ext_vector_type(8)));
     s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, r);

@@ -19,7 +19,7 @@
 // Rows past M are zeroed in the dx3 image (the DMA clamps them to a valid row): they add nothing to
 // dW or the statistics, and their dz2 rows are dropped by the store's range check.
 // Reference behaviour: autograd of torchvision's Bottleneck conv3 / bn3 under cuDNN.
-#include "ddl_common.h"
+#include "ddl_lds.h"
 
 #include <algorithm>
 
@@ -28,10 +28,6 @@ namespace {
 constexpr int NW = 8, NTH = NW * 64;
 constexpr int TM = 32;                          // rows per tile: one MFMA k-step of the wgrad
 constexpr int DPT = 6, SPT = 1;                 // DMA / store instructions per wave per tile
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct C3Params {
     const bf16_t* dz;      // [M][CO] gradient of bn3's output (ReLU mask applied)
@@ -53,49 +49,6 @@ struct C3Params {
     uint32_t dz2_bytes;
 };
 
-__device__ __forceinline__ void glds16(const void* g, char* dst) {
-    __builtin_amdgcn_global_load_lds(g, (lds_void*)dst, 16, 0, 2);   // nt: streamed once
-}
-__device__ __forceinline__ bf16x8 ds_read16(uint32_t addr) {
-    bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ uint2 ds_read8(uint32_t addr) {
-    uint2 v;
-    asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ s16x4 ds_read_tr8(uint32_t addr) {
-    s16x4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ uint32_t ds_read32(uint32_t addr) {
-    uint32_t v;
-    asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ void ds_write8(uint32_t addr, uint2 v) {
-    asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-__device__ __forceinline__ void ds_write16(uint32_t addr, u32x4 v) {
-    asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-
-// s_waitcnt vmcnt(n) for a workgroup-uniform run-time n
-__device__ __forceinline__ void wait_vm(int n) {
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-
 // 8 elements of dx = A dz + B x + D in the shared spelling of the apply pass (ddl_common.h), so the
 // bf16 image is bit-identical to the tensor that pass stores
 __device__ __forceinline__ u32x4 bn_apply8(bf16x8 dzv, bf16x8 xv, const float* A, const float* B, const float* D,
@@ -105,8 +58,8 @@ __device__ __forceinline__ u32x4 bn_apply8(bf16x8 dzv, bf16x8 xv, const float* A
     u32x4 o;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const float g0 = __uint_as_float(gw[i] << 16), g1 = __uint_as_float(gw[i] & 0xffff0000u);
-        const float x0 = __uint_as_float(xw[i] << 16), x1 = __uint_as_float(xw[i] & 0xffff0000u);
+        const float g0 = lo_f(gw[i]), g1 = hi_f(gw[i]);
+        const float x0 = lo_f(xw[i]), x1 = hi_f(xw[i]);
         const float o0 = bn_bwd_apply1(A[2 * i], g0, B[2 * i], x0, D[2 * i]);
         const float o1 = bn_bwd_apply1(A[2 * i + 1], g1, B[2 * i + 1], x1, D[2 * i + 1]);
         o[i] = pack2bf(o0, o1) & keep;
@@ -129,12 +82,12 @@ __global__ __launch_bounds__(NTH, 1) void conv3_bwd_k(C3Params p) {
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, r16 = lane & 15;
     const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-    const __amdgpu_buffer_rsrc_t crs =
-        __builtin_amdgcn_make_buffer_rsrc(p.dz2, 0, (int)p.dz2_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t crs = rsrc(p.dz2, p.dz2_bytes);
     const int t0 = blockIdx.x * p.chunk, t1 = min(p.tiles, t0 + p.chunk);
 
     // every wave issues DPT DMA instructions per tile: 2 of dz, 2 of x3 (1 KB = 2 rows each), one of
-    // a2 (waves 0-3) or x2 (waves 4-7) (1 KB = 8 rows), one of the mask (256 B, the same in every wave)
+    // a2 (waves 0-3) or x2 (waves 4-7) (1 KB = 8 rows), one of the mask (256 B, the same in every wave).
+    // Non-temporal: every row is streamed once
     auto prefetch = [&](int t, int buf) {
         char* base = smem + WBYTES + buf * BUFB;
         const long m0 = (long)t * TM;
@@ -142,13 +95,13 @@ __global__ __launch_bounds__(NTH, 1) void conv3_bwd_k(C3Params p) {
         for (int qq = 0; qq < 2; ++qq) {
             const int q = qq * NW + wv, r = q * 2 + (lane >> 5), c = (lane & 31) ^ (r & 15);
             const long gr = min(m0 + r, p.M - 1);          // rows past the end: any valid row
-            glds16(p.dz + gr * CO + c * 8, base + O_DZ + q * 1024);
-            glds16(p.x3 + gr * CO + c * 8, base + O_X3 + q * 1024);
+            glds16_nt(p.dz + gr * CO + c * 8, base + O_DZ + q * 1024);
+            glds16_nt(p.x3 + gr * CO + c * 8, base + O_X3 + q * 1024);
         }
         {
             const int q = wv & 3, r = q * 8 + (lane >> 3), c = (lane & 7) ^ (r & 7);
             const long gr = min(m0 + r, p.M - 1);
-            glds16((wv < 4 ? p.a2 : p.x2) + gr * CI + c * 8, base + (wv < 4 ? O_A2 : O_X2) + q * 1024);
+            glds16_nt((wv < 4 ? p.a2 : p.x2) + gr * CI + c * 8, base + (wv < 4 ? O_A2 : O_X2) + q * 1024);
         }
         {
             // TM rows x CI / 8 mask bytes = 256 contiguous bytes (the mask ends on a dword:
@@ -157,14 +110,15 @@ __global__ __launch_bounds__(NTH, 1) void conv3_bwd_k(C3Params p) {
             // matters is that each wave's DMA count per tile is the constant DPT the waits count
             const long b = min(m0 * (CI / 8) + lane * 4, p.M * (CI / 8) - 4);
             const uint8_t* src = p.mask2 ? p.mask2 + b : (const uint8_t*)p.a2;
-            __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)(base + O_MK), 4, 0, 0);
+            glds4(src, base + O_MK);
         }
     };
-    // W^T rows: 4 DMA instructions per wave
+    // W^T rows: 4 DMA instructions per wave (dma_rows<NW, CO, CI> without its row clamp, which no
+    // row here needs and which costs instructions)
 #pragma unroll
     for (int qq = 0; qq < CI / 2 / NW; ++qq) {
         const int q = qq * NW + wv, r = q * 2 + (lane >> 5), c = (lane & 31) ^ (r & 15);
-        glds16(p.wt + (long)r * CO + c * 8, smem + q * 1024);
+        glds16_nt(p.wt + (long)r * CO + c * 8, smem + q * 1024);
     }
 #pragma unroll
     for (int u = 0; u < NBUF - 1; ++u)
@@ -243,11 +197,11 @@ __global__ __launch_bounds__(NTH, 1) void conv3_bwd_k(C3Params p) {
         {
             const bf16x8 z0 = ds_read16(img + O_DZ + toff), z1 = ds_read16(img + O_DZ + toff + 16 * CO * 2);
             const bf16x8 x0 = ds_read16(img + O_X3 + toff), x1 = ds_read16(img + O_X3 + toff + 16 * CO * 2);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            LGKM0();
             __builtin_amdgcn_sched_barrier(0);
             ds_write16(img + O_DZ + toff, bn_apply8(z0, x0, cA, cB, cD, m0 + tr < p.M));
             ds_write16(img + O_DZ + toff + 16 * CO * 2, bn_apply8(z1, x1, cA, cB, cD, m0 + tr + 16 < p.M));
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            LGKM0();
             __builtin_amdgcn_s_barrier();
         }
 
@@ -263,7 +217,7 @@ __global__ __launch_bounds__(NTH, 1) void conv3_bwd_k(C3Params p) {
                     af[1][u] = ds_read16(img + O_DZ + aoff[1][k2 + u]);
                     bfr[u] = ds_read16(boff[k2 + u]);
                 }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                LGKM0();
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -291,7 +245,7 @@ __global__ __launch_bounds__(NTH, 1) void conv3_bwd_k(C3Params p) {
                 ev[i] = ds_read8(img + O_X2 + coff[i]);
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        LGKM0();
         __builtin_amdgcn_sched_barrier(0);
         {
             typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -319,16 +273,14 @@ __global__ __launch_bounds__(NTH, 1) void conv3_bwd_k(C3Params p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 float v[4] = {acc[i][0], acc[i][1], acc[i][2], acc[i][3]};
-                const float xv[4] = {__uint_as_float(ev[i].x << 16), __uint_as_float(ev[i].x & 0xffff0000u),
-                                     __uint_as_float(ev[i].y << 16), __uint_as_float(ev[i].y & 0xffff0000u)};
+                const float xv[4] = {lo_f(ev[i].x), hi_f(ev[i].x), lo_f(ev[i].y), hi_f(ev[i].y)};
                 const uint32_t bits = mword[i] >> mshift;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = ((bits >> e) & 1u) ? v[e] : 0.f;
                 const uint32_t lo = pack2bf(v[0], v[1]), hi = pack2bf(v[2], v[3]);
                 ds_write8(img + O_X2 + coff[i], make_uint2(lo, hi));
                 if (m0 + 16 * i + r16 < p.M) {
-                    const float tq[4] = {__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u),
-                                         __uint_as_float(hi << 16), __uint_as_float(hi & 0xffff0000u)};
+                    const float tq[4] = {lo_f(lo), hi_f(lo), lo_f(hi), hi_f(hi)};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         st_s[e] += tq[e];
@@ -337,13 +289,13 @@ __global__ __launch_bounds__(NTH, 1) void conv3_bwd_k(C3Params p) {
                 }
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        LGKM0();
         __builtin_amdgcn_s_barrier();
         // ---- the dz2 tile leaves as whole rows: 4 rows (512 B) per wave, one store instruction
         {
             const int row = 4 * wv + (lane >> 4), pc = lane & 15;
             const uint2 d = ds_read8(img + O_X2 + row * (CI * 2) + (((pc >> 1) ^ (row & 7)) << 4) + (pc & 1) * 8);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            LGKM0();
             __builtin_amdgcn_sched_barrier(0);
             const long grow = m0 + row;
             const uint32_t off = grow < p.M ? (uint32_t)((grow * CI + pc * 4) * 2) : 0x80000000u;

@@ -27,7 +27,7 @@
 //     workgroup instead of one per 128-pixel tile.
 // Reference behaviour: the convolutions of torchvision's Bottleneck
 // (reference: SURVEY.md §2.3 K1/K2 -- cuDNN implicit-GEMM convs under resnet50()).
-#include "ddl_common.h"
+#include "ddl_lds.h"
 
 #include <cstdlib>
 
@@ -41,8 +41,6 @@ constexpr int NRING = 6, ZSLOT = 6, NSLOT = 7;
 constexpr int WBYTES = 9 * CH * CH * 2;    // 72 KB
 constexpr int LDS_BYTES = WBYTES + NSLOT * ROWB;
 constexpr int STORES_PER_TILE = 4;         // pair stores per wave per tile (vmcnt accounting)
-
-typedef __attribute__((address_space(3))) void lds_void;
 
 struct C3Params {
     const bf16_t* x;        // [N, H, W, 64]
@@ -67,20 +65,10 @@ struct C3Params {
 // conflict-free, where the GEMM kernels' (r >> 1) & 7 is 2-way for odd starts.
 __device__ __forceinline__ int swz(int row) { return row & 7; }
 
-// LDS fragment read the compiler does not track (the caller places the lgkmcnt waits)
-__device__ __forceinline__ bf16x8 ds_read16(uint32_t addr) {
-    bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-
-__device__ __forceinline__ void glds(const bf16_t* g, char* dst) {
-    __builtin_amdgcn_global_load_lds((const void*)g, (lds_void*)dst, 16, 0, 2);   // nt: rows are staged once
-}
-
 // LDS-DMA of input row h of image n into ring slot `slot`: W/8 wave instructions of
 // 1 KB (8 pixels x 8 chunks), spread over the 4 waves; the chunk swizzle is applied on
-// the source address so the DMA image stays lane-linear.
+// the source address so the DMA image stays lane-linear.  (Non-temporal, here and in every DMA
+// of this file: rows are staged once.)
 __device__ __forceinline__ void issue_row(const C3Params& p, char* smem, int n, int h, int slot, int wv, int lane) {
     char* base = smem + WBYTES + slot * ROWB + 128;    // pixel slot 1 = w 0
     const bf16_t* src = p.x + ((long)n * p.H + h) * p.W * CH;
@@ -88,7 +76,7 @@ __device__ __forceinline__ void issue_row(const C3Params& p, char* smem, int n, 
     for (int q = wv; q < nq; q += 4) {
         const int px = q * 8 + (lane >> 3);            // w
         const int c = (lane & 7) ^ swz(px + 1);
-        glds(src + px * CH + c * 8, base + q * 1024);
+        glds16_nt(src + px * CH + c * 8, base + q * 1024);
     }
 }
 
@@ -107,7 +95,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_k(C3Params p) {
     for (int q = wv; q < 72; q += 4) {                 // 1 KB = 8 weight rows of one tap
         const int t = q >> 3, k = (q & 7) * 8 + (lane >> 3);
         const int c = (lane & 7) ^ swz(k);
-        glds(p.w + ((long)k * 9 + t) * CH + c * 8, smem + q * 1024);
+        glds16_nt(p.w + ((long)k * 9 + t) * CH + c * 8, smem + q * 1024);
     }
 
     // BNB: this lane's BatchNorm mean / inverse std (fixed columns for the whole kernel)
@@ -145,7 +133,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_k(C3Params p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) st_s[j][r] = st_q[j][r] = 0.f;
 
-    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t yrs = rsrc(p.y, p.y_bytes);
     const int t0 = blockIdx.x * p.chunk, t1 = min(p.tiles, t0 + p.chunk);
     int sl[4] = {ZSLOT, ZSLOT, ZSLOT, ZSLOT};
     int ptr = 0;
@@ -297,7 +285,6 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_k(C3Params p) {
                 const int ws = (lane & 16) ? w : w - 16;
                 const bool sok = hok && ws < p.W;
                 const uint32_t off = sok && !(p.dbg & 1) ? (uint32_t)(((rowpix + ws) * CH + nb + (lane >> 5) * 8) * 2) : 0x80000000u;
-                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
                 const u32x4 d = {xs[0], ys[0], xs[1], ys[1]};
                 __builtin_amdgcn_raw_buffer_store_b128(d, yrs, (int)off, 0, 0);
             }
@@ -353,21 +340,6 @@ struct C3WParams {
     int dbg;
 };
 
-// transposing LDS read (ds_read_b64_tr_b16) the compiler does not track: the caller waits
-// (lgkmcnt) by hand -- tracked reads drew lgkmcnt(0) waits in the middle of the MFMA stream
-__device__ __forceinline__ s16x4 ds_read_tr(uint32_t addr) {
-    s16x4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-// k-major fragment (rows = the image's columns) from the two tr reads at LDS addresses a, b
-__device__ __forceinline__ bf16x8 tr_frag(uint32_t a, uint32_t b) {
-    const s16x4 lo = ds_read_tr(a), hi = ds_read_tr(b);
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
-}
-
 // dy rows h0, h0 + 1 of image n into dy image `buf` (pixel slot swizzle: slot & 7)
 __device__ __forceinline__ void issue_dy(const C3WParams& p, char* smem, int n, int h0, int buf, int wv, int lane) {
     char* base = smem + NSLOT * ROWB + buf * DYB;
@@ -378,7 +350,7 @@ __device__ __forceinline__ void issue_dy(const C3WParams& p, char* smem, int n, 
         for (int q = wv; q < nq; q += 4) {
             const int px = q * 8 + (lane >> 3);
             const int c = (lane & 7) ^ (px & 7);
-            glds(src + px * CH + c * 8, base + rr * 8192 + q * 1024);
+            glds16_nt(src + px * CH + c * 8, base + rr * 8192 + q * 1024);
         }
     }
 }
@@ -390,7 +362,7 @@ __device__ __forceinline__ void issue_xrow(const C3WParams& p, char* smem, int n
     for (int q = wv; q < nq; q += 4) {
         const int px = q * 8 + (lane >> 3);
         const int c = (lane & 7) ^ swz(px + 1);
-        glds(src + px * CH + c * 8, base + q * 1024);
+        glds16_nt(src + px * CH + c * 8, base + q * 1024);
     }
 }
 

@@ -24,7 +24,7 @@
 // Split-K writes fp32 partial slabs reduced (with the epilogue) by gemm_reduce.
 // Block ids are remapped so the blocks that share an XCD's L2 (ids congruent
 // mod 8) walk neighbouring tiles (bijective remap, §5.5 T1).
-#include "ddl_common.h"
+#include "ddl_lds.h"
 
 #include <cstdlib>
 
@@ -93,7 +93,7 @@ __device__ __forceinline__ uint4 sel(bool ok, uint4 a, uint4 z) {
     return make_uint4(ok ? a.x : z.x, ok ? a.y : z.y, ok ? a.z : z.z, ok ? a.w : z.w);
 }
 
-__device__ __forceinline__ int swz_ko(int r) { return 2 * ((r & 3) | (((r >> 3) & 1) << 2)); }
+// (swz_ko, the 256-byte-row k-outer swizzle: ddl_lds.h)
 // 64-column k-major image (narrow B operand), 128-byte rows: a fragment read touches rows
 // 8g + q (g, q < 4), two chunks each; rows of one parity share a bank half, so the chunk
 // pair is XORed with (q >> 1) | (g & 1) << 1 -- the same 2-way (g, g + 2) overlap as the
@@ -279,7 +279,6 @@ __device__ __forceinline__ bf16x8 read_frag(const char* lds, int rbase, int kk) 
         const int chunk = col >> 3;
         const int r_a = kk * 32 + 8 * g + q;
         const int r_b = r_a + 4;
-        typedef __attribute__((address_space(3))) s16x4 lds_v4;
         const char* pa = NARROW ? lds + r_a * 128 + ((chunk ^ swz_kon(r_a)) << 4) + (pq & 1) * 8
                                 : lds + r_a * 256 + ((chunk ^ swz_ko(r_a)) << 4) + (pq & 1) * 8;
         const char* pb = NARROW ? lds + r_b * 128 + ((chunk ^ swz_kon(r_b)) << 4) + (pq & 1) * 8

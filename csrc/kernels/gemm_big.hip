@@ -31,7 +31,7 @@
 //     stays lane-linear and every fragment read is conflict-free;
 //   * split-K over blockIdx.y with fp32 partial slabs reduced (with the
 //     epilogue) by a second kernel; XCD-aware bijective block remap.
-#include "ddl_common.h"
+#include "ddl_lds.h"
 
 #include <cstdlib>
 #include <mutex>
@@ -57,9 +57,6 @@ constexpr int HALF = 128 * 64 * 2;   // 16 KB half-tile
 
 enum Layout { KC = 0, KO = 1, CONV = 2, CONVW = 3 };
 enum Act { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2, ACT_TANH = 3, ACT_DGELU = 4, ACT_BNB = 5 };
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(3))) s16x4 lds_v4;
 
 struct ConvDesc {
     int N, H, W, C;
@@ -104,13 +101,8 @@ constexpr int SCHED_STRIDE = 32;
 enum EpiKind { EK_GEN = 0, EK_BF16 = 1, EK_F32 = 2, EK_GELU = 3, EK_DGELU = 4, EK_BNB = 5, EK_BNBC = 6 };
 
 __device__ __forceinline__ int half_off(int buf, int x, int h) { return ((buf * 2 + x) * 2 + h) * HALF; }
-__device__ __forceinline__ int swz_kc(int b) { return b ^ (((b >> 9) & 1) << 5); }
-__device__ __forceinline__ int swz_ko(int r) { return 2 * ((r & 3) | (((r >> 3) & 1) << 2)); }
-
-__device__ __forceinline__ void glds(const bf16_t* g, char* dst) {
-    __builtin_amdgcn_global_load_lds((const void*)g, (lds_void*)dst, 16, 0, 0);
-}
-
+// (the operand DMA is glds16, the default cache policy: tiles are re-read by the workgroups of the
+// same tile row / column and by the implicit GEMM's taps -- profiles/dma_nt_ab.log)
 // pixel decomposition of a GEMM row m (conv): image pointer + top-left input coords
 struct Pix {
     const bf16_t* img;
@@ -214,14 +206,14 @@ struct Stager {
                 const bf16_t* g = lp[h] + off;
                 if (ktail) g = (off + kcol < K) ? g : p.zero;
                 if (!IS_A && h == 1 && zero_h1) g = p.zero;
-                glds(g, hbase + (w * 2 + j) * 1024);
+                glds16(g, hbase + (w * 2 + j) * 1024);
             }
         } else if (L == KO) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const bf16_t* g = lp[h] + (long)(kt * BK + j * 4) * ld;
                 if (ktail) g = (kt * BK + j * 4 + (w * 2) * 4 + (l >> 4) < K) ? g : p.zero;
-                glds(g, hbase + (w * 2 + j) * 1024);
+                glds16(g, hbase + (w * 2 + j) * 1024);
             }
         } else if (L == CONV) {
             const Pix& x = px[h];
@@ -233,7 +225,7 @@ struct Stager {
                 const bool ok = (unsigned)(x.hb + dh) < (unsigned)p.cd.H && (unsigned)(x.wb + dw) < (unsigned)p.cd.W;
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
-                    glds(ok ? lp[h] + toff + j * 32 : p.zero, hbase + (w * 2 + j) * 1024);
+                    glds16(ok ? lp[h] + toff + j * 32 : p.zero, hbase + (w * 2 + j) * 1024);
             } else {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
@@ -242,7 +234,7 @@ struct Stager {
                     tap_of(p.cd, k < K ? k : 0, dh, dw, ci);
                     const int hh = x.hb + dh, ww = x.wb + dw;
                     const bool ok = k < K && (unsigned)hh < (unsigned)p.cd.H && (unsigned)ww < (unsigned)p.cd.W;
-                    glds(ok ? x.img + ((long)hh * p.cd.W + ww) * p.cd.C + ci : p.zero, hbase + (w * 2 + j) * 1024);
+                    glds16(ok ? x.img + ((long)hh * p.cd.W + ww) * p.cd.C + ci : p.zero, hbase + (w * 2 + j) * 1024);
                 }
             }
         } else {   // CONVW: reduction rows are output pixels, columns are (tap, channel)
@@ -262,21 +254,11 @@ struct Stager {
                     if ((unsigned)hh < (unsigned)p.cd.H && (unsigned)ww < (unsigned)p.cd.W)
                         g = x.img + ((long)hh * p.cd.W + ww) * p.cd.C + ci;
                 }
-                glds(g, hbase + (w * 2 + j) * 1024);
+                glds16(g, hbase + (w * 2 + j) * 1024);
             }
         }
     }
 };
-
-// Transposed LDS read through a restrict-qualified parameter: inlined, the read
-// carries alias-scope metadata, which is what keeps the compiler's LDS-DMA tracking
-// from putting an `s_waitcnt vmcnt(0)` in front of every ds_read_b64_tr_b16 (a bare
-// builtin read has no alias info, so it waited out ALL in-flight operand DMA -- the
-// whole 3-half-tile prefetch of the reduction-outer (NN / TN) kernels, every phase).
-// The schedule's own counted vmcnt waits + barriers order DMA and reads.
-__device__ __forceinline__ s16x4 ds_read_tr(lds_v4* __restrict__ p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16(p);
-}
 
 // fragment: operand rows rbase..rbase+15 of half h, k = 32 kk + 8 (lane>>4) + 0..7
 template <int L>
@@ -286,21 +268,22 @@ __device__ __forceinline__ bf16x8 frag(const char* hbase, int rbase, int kk) {
         const int pb = swz_kc((l & 15) * 64 + (l >> 4) * 16);
         return *reinterpret_cast<const bf16x8*>(hbase + ((rbase >> 4) * 2 + kk) * 1024 + pb);
     } else {
+        // frag_ko (ddl_lds.h) of k-rows 32 kk .. + 31, spelled out: through frag_ko the 8-wave kernels
+        // allocate their registers differently
         const int g = l >> 4, q = (l >> 2) & 3, pq = l & 3;
         const int col = rbase + 4 * pq;
         const int chunk = col >> 3;
         const int ra = kk * 32 + 8 * g + q, rb = ra + 4;
         const char* pa = hbase + ra * 256 + ((chunk ^ swz_ko(ra)) << 4) + (pq & 1) * 8;
         const char* pb = hbase + rb * 256 + ((chunk ^ swz_ko(rb)) << 4) + (pq & 1) * 8;
-        s16x4 lo = ds_read_tr((lds_v4*)pa);
-        s16x4 hi = ds_read_tr((lds_v4*)pb);
+        s16x4 lo = lds_read_tr((lds_v4*)pa);
+        s16x4 hi = lds_read_tr((lds_v4*)pb);
         typedef short s16x8 __attribute__((ext_vector_type(8)));
         s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         return __builtin_bit_cast(bf16x8, r);
     }
 }
 
-#define BARRIER() __builtin_amdgcn_s_barrier()
 // End of a read phase.  With the staggered wave groups a half-tile may be
 // restaged by the other group in the very next phase, so this wave's fragment
 // reads must have completed BEFORE it arrives at the barrier (WAR); the wait
@@ -310,9 +293,7 @@ __device__ __forceinline__ bf16x8 frag(const char* hbase, int rbase, int kk) {
 #else
 #define READS_DONE_BARRIER() do { BARRIER(); LGKM0(); } while (0)
 #endif
-#define LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #define VM6() asm volatile("s_waitcnt vmcnt(6)" ::: "memory")
-#define VMN(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 #define VM0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
 // Diagnostic build only (-DDDL_GEMM_STAMPS, csrc/bench/gemm_stamps.cpp): waves 0 and 4 record
@@ -1362,9 +1343,7 @@ constexpr int WG_TBL_BYTES = 160 * 1024 - WG_ST * 3 * WG_HALF;   // 64 KB: 8192 
 // operand tile, before each record (that version ran 1.5x SLOWER than the decomposing loader).  The
 // caller waits lgkmcnt(0) itself before using the value.
 __device__ __forceinline__ uint2 wg_row_rec(uint32_t lds_addr) {
-    uint2 v;
-    asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"(lds_addr));
-    return v;
+    return ds_read8(lds_addr);
 }
 
 template <bool CW, bool TBL = false>
@@ -1423,8 +1402,8 @@ __global__ __launch_bounds__(256, 1) void gemm_wg_k(BigParams p) {
                 rec[j] = wg_row_rec((uint32_t)(uintptr_t)(smem + RING) + ((int)ka - kt0 * WG_BK + krow0 + j * 4) * 8);
 #pragma unroll
             for (int j = 0; j < JW; ++j) {
-                glds(ga + (ka + j * 4) * p.lda, smem + wg_off(st, 0, 0) + (w * JW + j) * 1024);
-                glds(ga + (ka + j * 4) * p.lda + 128, smem + wg_off(st, 0, 1) + (w * JW + j) * 1024);
+                glds16(ga + (ka + j * 4) * p.lda, smem + wg_off(st, 0, 0) + (w * JW + j) * 1024);
+                glds16(ga + (ka + j * 4) * p.lda + 128, smem + wg_off(st, 0, 1) + (w * JW + j) * 1024);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
@@ -1434,24 +1413,24 @@ __global__ __launch_bounds__(256, 1) void gemm_wg_k(BigParams p) {
                 for (int h = 0; h < BH; ++h) {
                     const int hh = (int)(short)(rec[j].y & 0xffffu) + cdh[h], ww = ((int)rec[j].y >> 16) + cdw[h];
                     const bool ok = (unsigned)hh < (unsigned)p.cd.H && (unsigned)ww < (unsigned)p.cd.W;
-                    glds(ok ? p.B + ((int)rec[j].x + toff[h]) : p.zero, smem + wg_off(st, 1, h) + (w * JW + j) * 1024);
+                    glds16(ok ? p.B + ((int)rec[j].x + toff[h]) : p.zero, smem + wg_off(st, 1, h) + (w * JW + j) * 1024);
                 }
             return;
         }
 #pragma unroll
         for (int j = 0; j < JW; ++j) {
-            glds(ga + (ka + j * 4) * p.lda, smem + wg_off(st, 0, 0) + (w * JW + j) * 1024);
-            glds(ga + (ka + j * 4) * p.lda + 128, smem + wg_off(st, 0, 1) + (w * JW + j) * 1024);
+            glds16(ga + (ka + j * 4) * p.lda, smem + wg_off(st, 0, 0) + (w * JW + j) * 1024);
+            glds16(ga + (ka + j * 4) * p.lda + 128, smem + wg_off(st, 0, 1) + (w * JW + j) * 1024);
 #pragma unroll
             for (int h = 0; h < BH; ++h) {
                 if (CW) {
                     const Pix x = decompose(p.cd, p.B, (int)ka + krow0 + j * 4, p.K);
                     const int hh = x.hb + cdh[h], ww = x.wb + cdw[h];
                     const bool ok = (unsigned)hh < (unsigned)p.cd.H && (unsigned)ww < (unsigned)p.cd.W;
-                    glds(ok ? x.img + ((long)hh * p.cd.W + ww) * p.cd.C + cci[h] : p.zero,
+                    glds16(ok ? x.img + ((long)hh * p.cd.W + ww) * p.cd.C + cci[h] : p.zero,
                          smem + wg_off(st, 1, h) + (w * JW + j) * 1024);
                 } else {
-                    glds(gb + (ka + j * 4) * p.ldb + h * 128, smem + wg_off(st, 1, h) + (w * JW + j) * 1024);
+                    glds16(gb + (ka + j * 4) * p.ldb + h * 128, smem + wg_off(st, 1, h) + (w * JW + j) * 1024);
                 }
             }
         }

@@ -29,7 +29,7 @@
 //     with counters of its own), XCD-aware tile order (gemm_big.hip coords).
 // Needs N % 128 == 0, K % 32 == 0, lda / ldb / ldc % 8 == 0, 16-byte aligned operands, operands and
 // output under 2 GB; M is free (rows past M re-read row M - 1 and are not stored: buffer range checks).
-#include "ddl_common.h"
+#include "ddl_lds.h"
 
 #include <cstdlib>
 
@@ -43,9 +43,6 @@ constexpr int GROUP_M = 8;
 
 enum { LKC = 0, LKO = 1, LCONV = 2 };
 enum { E_BF16 = 0, E_GELU = 1, E_DGELU = 2, E_BNB = 3 };
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(3))) s16x4 lds_v4;
 
 struct DuoParams {
     const bf16_t* A;
@@ -77,48 +74,15 @@ struct DuoParams {
     const bf16_t* zero; // LCONV: 16 zero bytes (g_duo_zero), the source of padding pixels
 };
 
-__device__ __forceinline__ int swz_kc(int b) { return b ^ (((b >> 9) & 1) << 5); }
-__device__ __forceinline__ int swz_ko(int r) { return 2 * ((r & 3) | (((r >> 3) & 1) << 2)); }
-
-__device__ __forceinline__ void glds(const bf16_t* g, char* dst) {
-    // (default cache policy: the implicit-GEMM convolution re-reads every input pixel once per tap
-    // -- the non-temporal policy cost ResNet-50 2 %, profiles/dma_nt_ab.log)
-    __builtin_amdgcn_global_load_lds((const void*)g, (lds_void*)dst, 16, 0, 0);
-}
-__device__ __forceinline__ s16x4 ds_read_tr(lds_v4* __restrict__ p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16(p);
-}
-
 // 16 x 32 fragment of a subtile image (rows on lane & 15, k chunk lane >> 4)
 __device__ __forceinline__ bf16x8 frag_kc(const char* sub) {
     const int l = threadIdx.x & 63;
     return *reinterpret_cast<const bf16x8*>(sub + swz_kc((l & 15) * 64 + (l >> 4) * 16));
 }
-// 16 columns (cbase ..) x 32 k of a [32 k][128] k-outer image, transposed on read
-__device__ __forceinline__ bf16x8 frag_ko(const char* img, int cbase) {
-    const int l = threadIdx.x & 63;
-    const int g = l >> 4, q = (l >> 2) & 3, pq = l & 3;
-    const int chunk = (cbase + 4 * pq) >> 3;
-    const int ra = 8 * g + q, rb = ra + 4;
-    const char* pa = img + ra * 256 + ((chunk ^ swz_ko(ra)) << 4) + (pq & 1) * 8;
-    const char* pb = img + rb * 256 + ((chunk ^ swz_ko(rb)) << 4) + (pq & 1) * 8;
-    const s16x4 lo = ds_read_tr((lds_v4*)pa);
-    const s16x4 hi = ds_read_tr((lds_v4*)pb);
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
-}
-
-#define BARRIER() __builtin_amdgcn_s_barrier()
-#define VMN(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-
 // 16 zero bytes (static device storage is zero-initialised): the source of padding pixels.  An
 // out-of-range LDS-DMA buffer load does not write its lane's LDS bytes (they keep stale data), so
 // zeros must be loaded, not produced by the range check.
 __device__ __attribute__((aligned(16))) uint4 g_duo_zero[1];
-
-__device__ __forceinline__ float lo_f(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float hi_f(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
 
 template <int LA, int LB, int EK>
 __global__ __launch_bounds__(NTH, 2) void gemm_duo_k(DuoParams p) {
@@ -233,7 +197,9 @@ __global__ __launch_bounds__(NTH, 2) void gemm_duo_k(DuoParams p) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const bool ok = (vmask[s] >> tap) & 1u;
-                glds(ok ? abase[s] + toff : p.zero, sb + (4 * w + s) * 1024);
+                // (default cache policy: the implicit-GEMM convolution re-reads every input pixel once
+                // per tap -- the non-temporal policy cost ResNet-50 2 %, profiles/dma_nt_ab.log)
+                glds16(ok ? abase[s] + toff : p.zero, sb + (4 * w + s) * 1024);
             }
         } else {
 #pragma unroll
@@ -262,11 +228,12 @@ __global__ __launch_bounds__(NTH, 2) void gemm_duo_k(DuoParams p) {
     bf16x8 fa0[8], fb0[4], fa1[8], fb1[4];
     auto read_frags = [&](int slot, bf16x8 (&fa)[8], bf16x8 (&fb)[4]) {
         const char* sb = smem + slot * ST_BYTES;
+        const int lane = threadIdx.x & 63;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            fb[j] = LB == LKC ? frag_kc(sb + A_BYTES + (wn * 4 + j) * 1024) : frag_ko(sb + A_BYTES, wn * 64 + j * 16);
+            fb[j] = LB == LKC ? frag_kc(sb + A_BYTES + (wn * 4 + j) * 1024) : frag_ko(sb + A_BYTES, wn * 64 + j * 16, lane);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) fa[i] = LA == LKO ? frag_ko(sb + wm * 8192, i * 16) : frag_kc(sb + (wm * 8 + i) * 1024);
+        for (int i = 0; i < 8; ++i) fa[i] = LA == LKO ? frag_ko(sb + wm * 8192, i * 16, lane) : frag_kc(sb + (wm * 8 + i) * 1024);
     };
     auto mma_half = [&](int i0, bf16x8 (&fa)[8], bf16x8 (&fb)[4]) {
         __builtin_amdgcn_s_setprio(1);
@@ -345,8 +312,6 @@ __global__ __launch_bounds__(NTH, 2) void gemm_duo_k(DuoParams p) {
             for (int e = 0; e < 4; ++e) { bnm[j][e] = mv[e]; bns[j][e] = sv[e]; }
         }
     }
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     u32x2 rb[8][4];
     if (pre) {
         const __amdgpu_buffer_rsrc_t prs =

@@ -20,14 +20,14 @@
 // accumulate in registers over all of a workgroup's tiles: one partial row per workgroup.
 // Reference behaviour: the 1x1 convolutions of torchvision's Bottleneck under cuDNN
 // (SURVEY.md §2.3 K1/K2).
-#include "ddl_common.h"
+#include "ddl_lds.h"
 
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
 
-constexpr int TM = 64, NT = 256;
+constexpr int TM = 64, NT = 256, NW = NT / 64;
 // EPI_RESBNB (N = 256): residual added, then the BatchNorm backward as EPI_BNB -- the
 // BN input is register-prefetched a tile ahead (its LDS image would not fit beside the
 // residual's), the mask comes by LDS-DMA
@@ -36,9 +36,6 @@ template <int EPI>
 constexpr bool is_bnb() { return EPI == EPI_BNB || EPI == EPI_RESBNB; }
 template <int N>
 constexpr int mask_stride() { return TM * N / 8 > 1024 ? TM * N / 8 : 1024; }   // bytes per mask image
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct SkParams {
     const bf16_t* A;
@@ -54,53 +51,6 @@ struct SkParams {
     const float* istd;
     uint32_t c_bytes;
 };
-
-__device__ __forceinline__ void glds(const bf16_t* g, char* dst) {
-    __builtin_amdgcn_global_load_lds((const void*)g, (lds_void*)dst, 16, 0, 2);   // nt: streamed once
-}
-__device__ __forceinline__ bf16x8 ds_read16(uint32_t addr) {
-    bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ uint2 ds_read8(uint32_t addr) {
-    uint2 v;
-    asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ uint32_t ds_read32(uint32_t addr) {
-    uint32_t v;
-    asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ void ds_write8(uint32_t addr, uint2 v) {
-    asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-
-// swizzled [rows][K] bf16 image: 16-byte chunk c of row r at chunk c ^ (r & SWM)
-template <int K>
-constexpr int swm() { return K == 64 ? 7 : 15; }
-
-// NROWS rows of a [rows][K] bf16 matrix into a swizzled LDS image by LDS-DMA: a fixed
-// (compile-time) number of 1 KB instructions per wave, so the waits can count them
-template <int K, int NROWS>
-__device__ __forceinline__ void dma_rows(const bf16_t* src, long row0, long rows_valid, char* dst, int wv, int lane) {
-    constexpr int CPR = K / 8;                    // 16-byte chunks per row
-    constexpr int RPI = 64 / CPR;                 // rows per 1 KB wave instruction
-    constexpr int NINST = NROWS / RPI;
-    static_assert(NINST % 4 == 0, "instructions split evenly over the 4 waves");
-#pragma unroll
-    for (int qq = 0; qq < NINST / 4; ++qq) {
-        const int q = qq * 4 + wv;
-        const int r = q * RPI + lane / CPR;
-        const int c = (lane % CPR) ^ (r & swm<K>());
-        const long gr = min(row0 + r, rows_valid - 1);   // rows past the end: any valid row
-        glds(src + gr * K + c * 8, dst + q * 1024);
-    }
-}
 
 template <int N, int K, int EPI>
 __global__ __launch_bounds__(NT) void skinny_gemm_k(SkParams p) {
@@ -129,8 +79,8 @@ __global__ __launch_bounds__(NT) void skinny_gemm_k(SkParams p) {
     // stores, so "this tile's DMA landed" is vmcnt(stores of the previous tile).  (A tile
     // is only ever waited for by the tile that prefetched it + 1, which exists.)
     auto prefetch = [&](int t, int buf) {
-        dma_rows<K, TM>(p.A, (long)t * TM, p.M, smem + OFF_A + buf * ABYTES, wv, lane);
-        if constexpr (EPI != EPI_PLAIN) dma_rows<N, TM>(eop, (long)t * TM, p.M, smem + OFF_C + buf * CBYTES, wv, lane);
+        dma_rows<NW, K, TM>(p.A, (long)t * TM, p.M, smem + OFF_A + buf * ABYTES, wv, lane);
+        if constexpr (EPI != EPI_PLAIN) dma_rows<NW, N, TM>(eop, (long)t * TM, p.M, smem + OFF_C + buf * CBYTES, wv, lane);
         if constexpr (is_bnb<EPI>()) {
             // 64 rows x N/8 mask bytes (512 B / 2 KB) as 4-byte-per-lane DMA instructions (the
             // mask ends on a dword: clamping never misplaces a valid row's bytes); every
@@ -140,8 +90,7 @@ __global__ __launch_bounds__(NT) void skinny_gemm_k(SkParams p) {
             for (int k = 0; k < TM * N / 8 / 256; ++k) {
                 const long b = min(byte0 + (long)(k * 64 + lane) * 4, last);
                 const uint8_t* src = p.mask ? p.mask + b : (const uint8_t*)p.A;
-                __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)(smem + OFF_M + buf * MS + k * 256), 4, 0,
-                                                 0);
+                glds4(src, smem + OFF_M + buf * MS + k * 256);
             }
         }
     };
@@ -161,7 +110,7 @@ __global__ __launch_bounds__(NT) void skinny_gemm_k(SkParams p) {
                 dst[i][j] = *reinterpret_cast<const uint2*>(p.aux + row * N + cb + 16 * j + 4 * g);
         }
     };
-    dma_rows<K, N>(p.B, 0, N, smem, wv, lane);
+    dma_rows<NW, K, N>(p.B, 0, N, smem, wv, lane);
     if (t0 < t1) {
         prefetch(t0, 0);
         if constexpr (EPI == EPI_RESBNB) prefetch_x(t0, xa);

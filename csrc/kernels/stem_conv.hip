@@ -47,7 +47,7 @@
 //     of the tap/channel index), accumulating into the gradient sink.
 // Reference behaviour: the stem conv of torchvision's resnet50 (reference: SURVEY.md §2.3 --
 // the cuDNN weight-gradient kernel under loss.backward()).
-#include "ddl_common.h"
+#include "ddl_lds.h"
 
 namespace {
 
@@ -60,8 +60,6 @@ constexpr int STAGE = NWV * NI * 1024; // 48 KB
 constexpr int XS_OFF = 28672;          // xs block offset in a stage (dy block: 2 Q x 128 B, Q <= 112)
 constexpr int NSTAGE = 3;
 
-typedef __attribute__((address_space(3))) void lds_void;
-
 __device__ uint4 g_stem_zero[2];       // zero page for the filler lanes (never written)
 
 struct StemWParams {
@@ -72,19 +70,6 @@ struct StemWParams {
 };
 
 __device__ __forceinline__ int dswz(int row) { return 2 * ((row >> 1) & 3); }
-
-// transposing LDS read the compiler does not track: the caller places the lgkmcnt waits
-__device__ __forceinline__ s16x4 ds_read_tr(uint32_t addr) {
-    s16x4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ bf16x8 tr_frag(uint32_t a, uint32_t b) {
-    const s16x4 lo = ds_read_tr(a), hi = ds_read_tr(b);
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
-}
 
 template <int QS>
 __global__ __launch_bounds__(NT, 1) void stem_wgrad_k(StemWParams p) {
@@ -114,6 +99,8 @@ __global__ __launch_bounds__(NT, 1) void stem_wgrad_k(StemWParams p) {
             } else if (u >= XS_OFF / 16 && u < XS_OFF / 16 + XSCH) {
                 src = xst + (u - XS_OFF / 16) * 8;
             }
+            // glds16_nt spelled out: through the inlined wrapper this kernel's address code compiles
+            // differently
             __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)(base + d * 1024), 16, 0, 2);   // nt
         }
     };
@@ -236,14 +223,6 @@ struct StemFParams {
     int P, tiles, chunk;   // tiles = N * P / 4 row quads
 };
 
-// untracked 16-byte LDS read with a compile-time offset (a per-lane base + immediates keeps the
-// 8 x QS fragment addresses of a tile out of the register file)
-template <int OFF>
-__device__ __forceinline__ bf16x8 ds_read16(uint32_t addr) {
-    bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
 template <int I, int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (I < N) {
@@ -287,7 +266,7 @@ __global__ __launch_bounds__(NT, 1) void stem_fwd_k(StemFParams p) {
             const int d = wv + NWV * k, u = d * 64 + lane;
             const int row = u >> 8, px = (u >> 1) & 127, h = (u & 1) ^ ((px >> 3) & 1);
             const bf16_t* src = px < WX && row < 7 ? xst + (row * WX + px) * SC + 8 * h : (const bf16_t*)g_stem_zero;
-            __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)(base + d * 1024), 16, 0, 2);   // nt
+            glds16_nt(src, base + d * 1024);   // nt: staged once
         }
     };
     // B fragment (pixels = columns): lane reads pixel 16 mb + r16 + s of tap row r, s = 2 (t & 1) +
@@ -326,7 +305,7 @@ __global__ __launch_bounds__(NT, 1) void stem_fwd_k(StemFParams p) {
             constexpr int mb = decltype(mbc)::value;
             static_for<0, 8>([&](auto tc) {
                 constexpr int t = decltype(tc)::value;
-                b[t] = ds_read16<(t >> 1) * FROW + mb * 512>(ra[t & 1]);
+                b[t] = ds_read16_off<(t >> 1) * FROW + mb * 512>(ra[t & 1]);
             });
         };
         read_mb(std::integral_constant<int, 0>{}, fb[0]);

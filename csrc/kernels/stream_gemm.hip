@@ -25,7 +25,7 @@
 //   * BatchNorm sums accumulate in registers over all of a workgroup's tiles; a wave owns whole
 //     columns, so each workgroup writes one partial row with no cross-wave reduction.
 // Reference behaviour: torchvision Bottleneck 1x1 convolutions under cuDNN.
-#include "ddl_common.h"
+#include "ddl_lds.h"
 
 #include <algorithm>
 
@@ -33,9 +33,6 @@ namespace {
 
 constexpr int NW = 8, NTH = NW * 64;
 enum Epi { EPI_PLAIN = 0, EPI_BNB = 2, EPI_RESBNB = 3 };
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct StParams {
     const bf16_t* A;
@@ -51,58 +48,6 @@ struct StParams {
     const float* istd;
     uint32_t c_bytes;
 };
-
-__device__ __forceinline__ void glds(const void* g, char* dst, int bytes) {
-    if (bytes == 16) __builtin_amdgcn_global_load_lds(g, (lds_void*)dst, 16, 0, 2);   // nt: streamed once
-    else __builtin_amdgcn_global_load_lds(g, (lds_void*)dst, 4, 0, 0);
-}
-__device__ __forceinline__ bf16x8 ds_read16(uint32_t addr) {
-    bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ uint2 ds_read8(uint32_t addr) {
-    uint2 v;
-    asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ uint32_t ds_read32(uint32_t addr) {
-    uint32_t v;
-    asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ void ds_write8(uint32_t addr, uint2 v) {
-    asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-
-// swizzled [rows][W] bf16 image: 16-byte chunk c of row r sits at chunk c ^ (r & swm): the 16
-// rows a ds_read_b128 lane group touches land on 16 distinct 16-byte slots of the bank row
-template <int W>
-constexpr int swm() { return W / 8 >= 16 ? 15 : W / 8 - 1; }
-
-// NROWS rows of W bf16 columns (row stride LD elements) into a swizzled [NROWS][W] LDS image by
-// LDS-DMA: a fixed (compile-time) number of 1 KB instructions per wave, so the waits can count them
-template <int W, int NROWS, long LD = W>
-__device__ __forceinline__ void dma_rows(const bf16_t* src, long row0, long rows_valid, char* dst, int wv, int lane,
-                                         long ld = LD) {
-    constexpr int CPR = W / 8;                    // 16-byte chunks per row
-    constexpr int RPI = CPR >= 64 ? 1 : 64 / CPR; // rows per 1 KB wave instruction
-    constexpr int IPR = CPR >= 64 ? CPR / 64 : 1; // instructions per row (W > 512)
-    constexpr int NINST = NROWS * IPR / RPI;
-    static_assert(NINST % NW == 0, "instructions split evenly over the waves");
-#pragma unroll
-    for (int qq = 0; qq < NINST / NW; ++qq) {
-        const int q = qq * NW + wv;
-        const int r = (q / IPR) * RPI + (CPR >= 64 ? 0 : lane / CPR);
-        const int cl = CPR >= 64 ? (q % IPR) * 64 + lane : lane % CPR;
-        const int c = cl ^ (r & swm<W>());
-        const long gr = min(row0 + r, rows_valid - 1);   // rows past the end: any valid row
-        glds(src + gr * ld + c * 8, dst + q * 1024, 16);
-    }
-}
 
 // NT = the whole output width, NB = the column slab one workgroup owns (NT / NB slabs; the slabs of
 // one row chunk are workgroups b, b + 8, ... -- one XCD under round-robin placement, so they share
@@ -141,9 +86,9 @@ __global__ __launch_bounds__(NTH, 1) void stream_gemm_k(StParams p) {
 
     const int t0 = chunk * p.chunk, t1 = min(p.tiles, t0 + p.chunk);
     auto prefetch = [&](int t, int buf) {
-        dma_rows<K, TM>(p.A, (long)t * TM, p.M, smem + OFF_A + buf * ABYTES, wv, lane);
+        dma_rows<NW, K, TM>(p.A, (long)t * TM, p.M, smem + OFF_A + buf * ABYTES, wv, lane);
         if constexpr (EPI != EPI_PLAIN)
-            dma_rows<NB, TM, NT>(eop + n0, (long)t * TM, p.M, smem + OFF_C + buf * CBYTES, wv, lane);
+            dma_rows<NW, NB, TM, NT>(eop + n0, (long)t * TM, p.M, smem + OFF_C + buf * CBYTES, wv, lane);
         if constexpr (BNB) {
             // the slab's TM x NB/8 mask bytes as 4-byte-per-lane DMA instructions (a row's NB/8 bytes
             // are contiguous, rows NT/8 apart); every wave issues the same ones (identical data)
@@ -152,7 +97,7 @@ __global__ __launch_bounds__(NTH, 1) void stream_gemm_k(StParams p) {
                 const int wi = k * 64 + lane, row = min(wi / MWPR, TM - 1), wc = wi % MWPR;
                 const long r = min((long)t * TM + row, p.M - 1);
                 const uint8_t* src = p.mask ? p.mask + r * (NT / 8) + n0 / 8 + 4 * wc : (const uint8_t*)p.A;
-                glds(src, smem + OFF_M + buf * MS + k * 256, 4);
+                glds4(src, smem + OFF_M + buf * MS + k * 256);
             }
         }
     };
@@ -436,26 +381,6 @@ namespace {
 constexpr int WS_ROWS = 32;                      // K rows per ring slot
 constexpr int PANEL = WS_ROWS * 256;             // one 128-column panel of a slot: 8 KB
 
-__device__ __forceinline__ int swz_ko2(int r) { return 2 * ((r & 3) | (((r >> 3) & 1) << 2)); }
-
-typedef __attribute__((address_space(3))) s16x4 lds_s4;
-__device__ __forceinline__ s16x4 ds_read_tr4(lds_s4* __restrict__ p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16(p);
-}
-
-// 16 columns (rbase .. +15 of a panel) x 32 k-rows as an MFMA operand fragment: lane holds column
-// rbase + (lane & 15), k = 8 (lane >> 4) .. +7 (two transposed reads of 4 rows each)
-__device__ __forceinline__ bf16x8 frag_ko(const char* panel, int rbase, int lane) {
-    const int g = lane >> 4, q = (lane >> 2) & 3, pq = lane & 3;
-    const int col = rbase + 4 * pq, chunk = col >> 3;
-    const int ra = 8 * g + q, rb = ra + 4;
-    const s16x4 lo = ds_read_tr4((lds_s4*)(panel + ra * 256 + ((chunk ^ swz_ko2(ra)) << 4) + (pq & 1) * 8));
-    const s16x4 hi = ds_read_tr4((lds_s4*)(panel + rb * 256 + ((chunk ^ swz_ko2(rb)) << 4) + (pq & 1) * 8));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
-}
-
 struct WgParams {
     const bf16_t* A;     // [K][lda]
     const bf16_t* B;     // [K][ldb]
@@ -504,13 +429,13 @@ __global__ __launch_bounds__(512, 1) void stream_wgrad_k(WgParams p) {
             const int inst = d * 8 + w;              // 0 .. 8 (PA + PB) - 1
             const int pnl = inst >> 3, q = inst & 7;
             const int row = 4 * q + (lane >> 4);
-            const int c = (lane & 15) ^ swz_ko2(row);  // data chunk this lane's slot holds
+            const int c = (lane & 15) ^ swz_ko(row);  // data chunk this lane's slot holds
             const long k = k0 + (long)t * WS_ROWS + row;
             const bool isA = pnl < PA;
             const int col = (isA ? pnl : pnl - PA) * 128 + 8 * c;
             const bool ok = k < k1 && col < (isA ? M : N);
             const bf16_t* src = ok ? (isA ? p.A + k * p.lda + col : p.B + k * p.ldb + col) : p.zero;
-            __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)(base + pnl * PANEL + q * 1024), 16, 0, 2);
+            glds16_nt(src, base + pnl * PANEL + q * 1024);   // nt: every operand byte is read once
         }
     };
     f32x4 acc[FI][FJ];

@@ -24,10 +24,12 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def compile_asm(src: str, out: str) -> None:
+def compile_asm(src: str, out: str, include: str = "") -> None:
+    """`include`: a header directory searched before csrc/include (a source from another revision)."""
     sys.path.insert(0, os.path.join(ROOT, "csrc"))
     import build  # noqa: E402  (csrc/build.py: the library's per-file extra flags)
-    cmd = [build.HIPCC, *build.flags_for(src), "--cuda-device-only", "-S", src, "-o", out]
+    pre = ["-I", include] if include else []
+    cmd = [build.HIPCC, *pre, *build.flags_for(src), "--cuda-device-only", "-S", src, "-o", out]
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
 
 
