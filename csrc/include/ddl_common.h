@@ -20,6 +20,19 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // Launch-error helper: every C entry point returns the HIP error code (0 = ok).
 #define DDL_RETURN_LAUNCH() return (int)hipGetLastError()
 
+// Compute units of the current device (host code: sizes persistent and one-round grids); 256, the
+// MI355X's count, if the attribute cannot be read.
+inline int num_cus() {
+    static const int n = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
+            v = 256;
+        return v;
+    }();
+    return n;
+}
+
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 // the low / high bf16 of a packed pair
 __device__ __forceinline__ float lo_f(uint32_t u) { return __uint_as_float(u << 16); }

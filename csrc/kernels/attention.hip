@@ -1513,16 +1513,8 @@ __global__ __launch_bounds__(64 * MW, 1) void attn_bwd_med_k(const bf16_t* __res
 }  // namespace
 
 namespace {
-int num_cus() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-            v = 256;
-        return v;
-    }();
-    return n;
-}
-// DDL_ATTN_FUSED_BWD=0: the tiled forward and two-kernel backward for every S (A/B timing, tests)
+// DDL_ATTN_FUSED_BWD=0: the tiled forward and two-kernel backward for every S.
+// tests/test_attention_edges_gpu.py sets it to route short sequences through the tiled kernels.
 bool fused_bwd_enabled() {
     static const bool on = [] {
         const char* e = getenv("DDL_ATTN_FUSED_BWD");
@@ -1530,7 +1522,8 @@ bool fused_bwd_enabled() {
     }();
     return on;
 }
-// DDL_ATTN_MED=0: 128 < S <= 256 takes the tiled forward and two-kernel backward (A/B timing)
+// DDL_ATTN_MED=0: 128 < S <= 256 takes the tiled forward and two-kernel backward (the same test
+// sets it to run those lengths through the tiled kernels)
 bool med_enabled() {
     static const bool on = [] {
         const char* e = getenv("DDL_ATTN_MED");

@@ -29,7 +29,6 @@
 // (reference: SURVEY.md §2.3 K1/K2 -- cuDNN implicit-GEMM convs under resnet50()).
 #include "ddl_lds.h"
 
-#include <cstdlib>
 
 namespace {
 
@@ -56,7 +55,8 @@ struct C3Params {
     const float* istd;
     int has_res, has_mask;  // BNB: res / mask given (otherwise they point at aux, loaded and ignored)
     uint32_t y_bytes;
-    int dbg;                // DDL_CONV3X3_DBG bits (timing experiments only): 1 no stores, 2 no row DMA, 4 no MFMA, 8 no epilogue
+    int dbg;                // always 0: timing-experiment bits (1 no stores, 2 no row DMA, 4 no MFMA, 8 no epilogue) of a
+                            // retired switch; conv3x3_k<true> needs 2 more VGPRs (248 -> 250) without the tests
 };
 
 // 16-byte chunk swizzle of a 128-byte LDS row: chunk ^ (row & 7).  ds_read_b128 banks
@@ -337,7 +337,6 @@ struct C3WParams {
     const bf16_t* dy;      // [N, H, W, 64] output gradient
     float* part;           // [gridDim.x][576][64]
     int N, H, W, HP, tiles, chunk;
-    int dbg;
 };
 
 // dy rows h0, h0 + 1 of image n into dy image `buf` (pixel slot swizzle: slot & 7)
@@ -436,12 +435,12 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_wgrad_k(C3WParams p) {
                 if (h >= p.H) continue;
                 nsl[r] = ptr;
                 ptr = ptr == NRING - 1 ? 0 : ptr + 1;
-                if (!(p.dbg & 2)) issue_xrow(p, smem, n, h, nsl[r], wv, lane);
+                issue_xrow(p, smem, n, h, nsl[r], wv, lane);
             }
             if (h0 + 3 >= p.H)
                 for (int i = tid; i < 8192 / 16; i += NT)
                     reinterpret_cast<uint4*>(smem + NSLOT * ROWB + (buf ^ 1) * DYB + 8192)[i] = make_uint4(0u, 0u, 0u, 0u);
-            if (!(p.dbg & 2)) issue_dy(p, smem, n, h0 + 2, buf ^ 1, wv, lane);
+            issue_dy(p, smem, n, h0 + 2, buf ^ 1, wv, lane);
         }
 
         // 4 pixel k-steps of 32 (row ks >> 1, columns (ks & 1) * 32 ..): 9 taps x 4 k-blocks;
@@ -465,7 +464,6 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_wgrad_k(C3WParams p) {
         read_ks(0, fx[0], fd[0]);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            if (p.dbg & 4) break;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // step ks's reads
             __builtin_amdgcn_sched_barrier(0);
             const int c = ks & 1;
@@ -554,8 +552,6 @@ DDL_API int ddl_conv3x3(const void* x, const void* w, void* y, int N, int H, int
     p.mean = mean;
     p.istd = istd;
     p.y_bytes = (uint32_t)ybytes;
-    static const int dbg = getenv("DDL_CONV3X3_DBG") ? atoi(getenv("DDL_CONV3X3_DBG")) : 0;
-    p.dbg = dbg;
     if (aux) hipLaunchKernelGGL(conv3x3_k<true>, dim3(g), dim3(NT), 0, stream, p);
     else hipLaunchKernelGGL(conv3x3_k<false>, dim3(g), dim3(NT), 0, stream, p);
     const hipError_t e = hipGetLastError();
@@ -580,8 +576,6 @@ DDL_API int ddl_conv3x3_wgrad(const void* x, const void* dy, void* dw, int N, in
     g = (p.tiles + p.chunk - 1) / p.chunk;
     if (ws_elems < (long)g * 576 * 64) return -1;
     p.part = ws;
-    static const int dbg = getenv("DDL_CONV3X3_DBG") ? atoi(getenv("DDL_CONV3X3_DBG")) : 0;
-    p.dbg = dbg;
     hipLaunchKernelGGL(conv3x3_wgrad_k, dim3(g), dim3(NT), 0, stream, p);
     hipLaunchKernelGGL(conv3x3_wgrad_reduce_k, dim3(288), dim3(256), 0, stream, (const float*)ws, g, dw, out_f32,
                        accumulate);

@@ -816,16 +816,13 @@ DDL_API int ddl_maxpool_fwd(int dtype, const void* x, void* y, uint8_t* idx, int
                                                                      K, S, pad)));
     DDL_RETURN_LAUNCH();
 }
-// DDL_POOL_ROWS=0: the flat-index stem pooling kernels (A/B timing)
-static bool rows_form_enabled() {
-    static const bool on = [] { const char* e = getenv("DDL_POOL_ROWS"); return !(e && e[0] == '0'); }();
-    return on;
-}
+// The stem pooling kernels take one block per output (or input) row; the flat-index kernels are the
+// path for N * P (N * H) >= 2^31, which the row form's grid cannot hold
 DDL_API int ddl_bn_relu_maxpool(int dtype, const void* x, const float* scale, const float* shift, void* y,
                                 uint8_t* idx, uint8_t* mask, int N, int H, int W, int C, int P, int Q, hipStream_t st) {
     if (C % 8 || H != 2 * P || W != 2 * Q) return -1;
     const long tot = (long)N * P * Q * (C / 8);
-    if ((long)N * P < (1L << 31) && rows_form_enabled()) {
+    if ((long)N * P < (1L << 31)) {
         DISPATCH_T(dtype,
                    (bn_relu_maxpool_rows_k<bf16_t><<<N * P, 256, 0, st>>>(
                        (const bf16_t*)x, scale, shift, (bf16_t*)y, idx, mask, H, W, C, P, Q)),
@@ -844,7 +841,7 @@ DDL_API int ddl_maxpool_bwd(int dtype, const void* dy, const uint8_t* idx, void*
                             int Q, int K, int S, int pad, hipStream_t st) {
     if (C % 8) return -1;
     const long tot = (long)N * H * W * (C / 8);
-    if ((long)N * H < (1L << 31) && rows_form_enabled()) {
+    if ((long)N * H < (1L << 31)) {
         DISPATCH_T(dtype,
                    (maxpool_bwd_rows_k<bf16_t><<<N * H, 256, 0, st>>>(
                        (const bf16_t*)dy, idx, (bf16_t*)dx, H, W, C, P, Q, K, S, pad)),

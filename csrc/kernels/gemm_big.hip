@@ -1538,17 +1538,6 @@ void fill_conv(ConvDesc& cd, const int* d) {
     cd.fd_S = make_fastdiv((uint32_t)std::max(1, cd.S));
 }
 
-int num_cus() {
-    static int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                     hipSuccess || v <= 0)
-            v = 256;
-        return v;
-    }();
-    return n;
-}
-
 // DDL_GEMM_DYNAMIC=0 keeps the static tile striding of the persistent grid (A/B timing)
 bool dynamic_enabled() {
     static const bool on = [] {

@@ -13,7 +13,6 @@
 // fused residual add, fp32 statistics saved for backward; backward computes dx
 // per row and per-block dgamma/dbeta partials reduced by a second kernel.
 #include "ddl_common.h"
-#include <cstdlib>
 #include <mutex>
 #include <unordered_map>
 
@@ -262,45 +261,24 @@ __global__ __launch_bounds__(256) void bn_apply2_rows_k(const T* __restrict__ x,
 // CUs hold at once for THIS kernel (its occupancy), each thread looping over rows.  A fixed 2048
 // (8 per CU) left a second round wherever registers allow fewer: at 68 VGPRs (7 waves per SIMD)
 // 1792 blocks ran, then 256 more, one per CU, ran alone to finish the pass.
-// DDL_BN_ROWS_GRID=0 restores the fixed 2048 (A/B timing).
-static int cu_count() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-            v = 256;
-        return v;
-    }();
-    return n;
-}
-static bool rows_grid_fit() {
-    static const bool on = [] {
-        const char* e = getenv("DDL_BN_ROWS_GRID");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-static int rows_grid(long M, int C, const void* kernel = nullptr) {
+static int rows_grid(long M, int C, const void* kernel) {
     const long rpb = 256 / (C / 8);
     const long need = (M + rpb - 1) / rpb;
-    long cap = 2048;
-    if (kernel && rows_grid_fit()) {
-        static std::mutex mu;
-        static std::unordered_map<const void*, int> per_cu;
-        int nb = 0;
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            auto it = per_cu.find(kernel);
-            if (it == per_cu.end()) {
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, 0) != hipSuccess) nb = 8;
-                nb = std::min(8, std::max(1, nb));
-                per_cu.emplace(kernel, nb);
-            } else {
-                nb = it->second;
-            }
+    static std::mutex mu;
+    static std::unordered_map<const void*, int> per_cu;
+    int nb = 0;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = per_cu.find(kernel);
+        if (it == per_cu.end()) {
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, 0) != hipSuccess) nb = 8;
+            nb = std::min(8, std::max(1, nb));
+            per_cu.emplace(kernel, nb);
+        } else {
+            nb = it->second;
         }
-        cap = (long)nb * cu_count();
     }
+    const long cap = (long)nb * num_cus();
     return (int)std::max<long>(1, std::min<long>(cap, need));
 }
 static bool rows_ok(int C) { return C % 8 == 0 && 256 % (C / 8) == 0; }
@@ -1090,46 +1068,26 @@ __global__ __launch_bounds__(1024) void ln_colsum_k(const float* __restrict__ pa
 
 // slices for nblk partial rows: S = ceil(nblk / FIN_RPS), capped so the last arriver's pass over
 // the slice rows stays one round trip of 16 row lanes x 8 (ws holds S x 2C floats)
-// DDL_FIN_RPS (>= 32: the partial-row buffers hold ceil(nblk / 32) slice rows): rows per slice (A/B)
-static int fin_rps_target() {
-    static const int v = [] { const char* e = getenv("DDL_FIN_RPS"); return e ? std::max(32, atoi(e)) : FIN_RPS; }();
-    return v;
-}
-static int fin_slices(int nblk) {
-    const int t = fin_rps_target();
-    return std::max(1, std::min(128, (nblk + t - 1) / t));
-}
+static int fin_slices(int nblk) { return std::max(1, std::min(128, (nblk + FIN_RPS - 1) / FIN_RPS)); }
 static int fin_rps(int nblk) { return (nblk + fin_slices(nblk) - 1) / fin_slices(nblk); }
 // The merged launch took 7.6-8.3 us against 6.7 us for one finalize workgroup on <= 512 rows in
 // the round-5 kernel tables, but whole-step A/B prefers it for every row count: ResNet-50 +0.3 %
 // same-box, BERT-base neutral (profiles/merged_fin_ab.log) -- the single workgroup's long tail
-// delays the dependent apply launch.  DDL_BN_MERGED_FIN=0: never, =1: above 512 rows only, 2:
-// always (default).
-static int merged_mode() {
-    static const int m = [] { const char* e = getenv("DDL_BN_MERGED_FIN"); return e ? atoi(e) : 2; }();
-    return m;
-}
-// (each launch owns one window of TICKET_WIN arrival tickets, one per 64-channel group: wider
-// layers than TICKET_WIN * 64 channels take the collapse + single-pass finalize instead, so a
-// group index can never reach into the next launch's window or past the pool)
-static bool merged_finalize(int nblk, int C) {
-    const int m = merged_mode();
-    return (C + 63) / 64 <= TICKET_WIN && (m == 2 || (m == 1 && nblk > 512));
-}
+// delays the dependent apply launch.  So the merged finalize runs wherever it can.
+// Each launch owns one window of TICKET_WIN arrival tickets, one per 64-channel group, so a group
+// index can never reach into the next launch's window or past the pool.  The collapse +
+// single-workgroup finalize kernels remain the path for layers wider than TICKET_WIN * 64
+// channels, for a null ticket pool and for a workspace too small for the slice rows.
+static bool merged_finalize(int C) { return (C + 63) / 64 <= TICKET_WIN; }
 
-// Partial rows beyond this are first collapsed 32:1 (a single finalize block per
+// Partial rows beyond COLLAPSE_OVER are first collapsed 32:1 (a single finalize block per
 // 64 columns is too little parallelism for ~1000 rows).  The caller allocates
 // `part` with room for the collapsed rows behind the nblk partial rows.
-// DDL_BN_COLLAPSE_MIN overrides the threshold (collapse_partials and ddl_bn_partials_ws)
-static int collapse_env() {
-    static const int v = [] { const char* e = getenv("DDL_BN_COLLAPSE_MIN"); return e ? atoi(e) : 0; }();
-    return v;
-}
 // Up to COLLAPSE_OVER rows the single column-sum kernel reads every row itself (colsum64: 8 rows
 // in flight per thread, <= 4 round trips): the collapse launch cost more than it saved there
 // (BERT-base: 49 collapse launches of ~5 us per step for 128- and 512-row partials).
 constexpr int COLLAPSE_OVER = 512;
-static bool needs_collapse(int nblk) { return nblk > (collapse_env() > 0 ? collapse_env() : COLLAPSE_OVER); }
+static bool needs_collapse(int nblk) { return nblk > COLLAPSE_OVER; }
 static const float* collapse_partials(const float* part, int& nblk, int width, hipStream_t st,
                                       float* ws = nullptr) {
     if (!needs_collapse(nblk)) return part;
@@ -1148,7 +1106,7 @@ DDL_API int ddl_bn_fwd_from_partials(int dtype, const float* part, int nblk, lon
                                      const void* beta, float* running_mean, float* running_var, float momentum,
                                      float eps, float* save_mean, float* save_invstd, float* scale, float* shift,
                                      float* ws, long ws_elems, hipStream_t st) {
-    if (merged_finalize(nblk, C)) {
+    if (merged_finalize(C)) {
         const int S = fin_slices(nblk);
         int* tk = S > 1 ? fin_tickets() : nullptr;
         if (S == 1 || (tk && ws && ws_elems >= (long)S * 2 * C)) {
@@ -1244,7 +1202,7 @@ DDL_API int ddl_bn_apply(int dtype, const void* x, const void* res, const float*
 template <typename T>
 static void bwd_finalize(const float* part, int nblk, float* ws, int C, long M, const T* gamma, const float* invstd,
                          T* dgamma, T* dbeta, float* coef, int acc, hipStream_t st) {
-    if (merged_finalize(nblk, C)) {
+    if (merged_finalize(C)) {
         const int S = fin_slices(nblk);
         int* tk = S > 1 ? fin_tickets() : nullptr;
         if (S == 1 || tk) {
@@ -1451,29 +1409,23 @@ DDL_API int ddl_bn_bwd_pool(int dtype, const void* dy, const uint8_t* idx, const
 }
 
 // ---------------------------------------------------------------- LayerNorm
-// DDL_LN_FWD8=0: the wave-per-row bf16 forward (A/B timing)
-static bool ln_fwd8_enabled() {
-    static const bool on = [] { const char* e = getenv("DDL_LN_FWD8"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
+// bf16 rows of H = 768 / 1024 take ln_fwd8_k (8 rows per block); every other width, and fp32, the
+// wave-per-row ln_fwd_k
 template <typename T>
 static int ln_fwd_dispatch(const T* x, const T* res, long res_rows, const T* g, const T* b, T* y, float* mean,
                            float* rstd, long rows, int H, float eps, Drop drop, hipStream_t st) {
-    if constexpr (sizeof(T) == 2) {
-        if (ln_fwd8_enabled() && (H / 256 == 3 || H / 256 == 4)) {
-            const int grid8 = (int)((rows + 7) / 8);
-            if (H / 256 == 3) ln_fwd8_k<3><<<grid8, 256, 0, st>>>(x, res, res_rows, g, b, y, mean, rstd, rows, H, eps, drop);
-            else ln_fwd8_k<4><<<grid8, 256, 0, st>>>(x, res, res_rows, g, b, y, mean, rstd, rows, H, eps, drop);
-            return 0;
-        }
-    }
-    const int grid = (int)((rows + 3) / 4);
+    const int grid = (int)((rows + 3) / 4), grid8 = (int)((rows + 7) / 8);
     switch (H / 256) {
         case 1: ln_fwd_k<T, 1><<<grid, 256, 0, st>>>(x, res, res_rows, g, b, y, mean, rstd, rows, H, eps, drop); break;
         case 2: ln_fwd_k<T, 2><<<grid, 256, 0, st>>>(x, res, res_rows, g, b, y, mean, rstd, rows, H, eps, drop); break;
-        case 3: ln_fwd_k<T, 3><<<grid, 256, 0, st>>>(x, res, res_rows, g, b, y, mean, rstd, rows, H, eps, drop); break;
-        case 4: ln_fwd_k<T, 4><<<grid, 256, 0, st>>>(x, res, res_rows, g, b, y, mean, rstd, rows, H, eps, drop); break;
+        case 3:
+            if constexpr (sizeof(T) == 2) ln_fwd8_k<3><<<grid8, 256, 0, st>>>(x, res, res_rows, g, b, y, mean, rstd, rows, H, eps, drop);
+            else ln_fwd_k<T, 3><<<grid, 256, 0, st>>>(x, res, res_rows, g, b, y, mean, rstd, rows, H, eps, drop);
+            break;
+        case 4:
+            if constexpr (sizeof(T) == 2) ln_fwd8_k<4><<<grid8, 256, 0, st>>>(x, res, res_rows, g, b, y, mean, rstd, rows, H, eps, drop);
+            else ln_fwd_k<T, 4><<<grid, 256, 0, st>>>(x, res, res_rows, g, b, y, mean, rstd, rows, H, eps, drop);
+            break;
         case 5: ln_fwd_k<T, 5><<<grid, 256, 0, st>>>(x, res, res_rows, g, b, y, mean, rstd, rows, H, eps, drop); break;
         case 6: ln_fwd_k<T, 6><<<grid, 256, 0, st>>>(x, res, res_rows, g, b, y, mean, rstd, rows, H, eps, drop); break;
         case 8: ln_fwd_k<T, 8><<<grid, 256, 0, st>>>(x, res, res_rows, g, b, y, mean, rstd, rows, H, eps, drop); break;
@@ -1513,21 +1465,16 @@ DDL_API int ddl_ln_fwd(int dtype, const void* x, const void* res, long res_rows,
     DDL_RETURN_LAUNCH();
 }
 
-// rows per block (DDL_LN_BWD_ROWS, default 32: +0.6% BERT-base over 16, 64 -2%) and block cap (DDL_LN_BWD_MAXBLK, default 1024)
-static int ln_env(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v && atoi(v) > 0 ? atoi(v) : dflt;
-}
+// 32 rows per block (+0.6% BERT-base over 16; 64: -2%), at most 1024 blocks.
 // Blocks of ~32 rows, rounded UP to whole rounds of the blocks the CUs hold at once (2 per CU at the
 // 230-240 VGPRs of the H = 768 / 1024 kernels): ViT's 25216 rows made 788 blocks -- one full round
 // of 512 and a 276-block second one; now 1024 equal blocks of 24-25 rows (rpb = ceil(rows / nblk))
-// run two full rounds.  DDL_LN_BWD_ROUNDS=0: the plain count (A/B timing).
+// run two full rounds.
 DDL_API int ddl_ln_bwd_nblk(long rows) {
-    static const int rpb = ln_env("DDL_LN_BWD_ROWS", 32), cap = ln_env("DDL_LN_BWD_MAXBLK", 1024);
-    static const bool rounds = [] { const char* e = getenv("DDL_LN_BWD_ROUNDS"); return !(e && e[0] == '0'); }();
+    constexpr long rpb = 32, cap = 1024;
     long nblk = std::max<long>(1, std::min<long>(cap, (rows + rpb - 1) / rpb));
-    const long slots = 2L * cu_count();
-    if (rounds && nblk > slots && nblk % slots) nblk = std::min<long>(std::max<long>(cap, slots), (nblk + slots - 1) / slots * slots);
+    const long slots = 2L * num_cus();
+    if (nblk > slots && nblk % slots) nblk = std::min<long>(std::max<long>(cap, slots), (nblk + slots - 1) / slots * slots);
     return (int)std::min<long>(nblk, rows);
 }
 
@@ -1562,7 +1509,7 @@ static int ln_bwd_dispatch(const T* dy, const T* x, const T* res, long res_rows,
     }
 #undef LNB_KNOWN
 #undef LNB
-    if (merged_finalize(nblk, H)) {
+    if (merged_finalize(H)) {
         // one launch: 128-row slices + last-arriver combine (ws: the room behind the partial rows)
         const int S = fin_slices(nblk);
         int* tk = S > 1 ? fin_tickets() : nullptr;
@@ -1727,7 +1674,7 @@ DDL_API int ddl_bn_bwd_finish(int dtype, const void* dy, const void* mask, const
 static int bn_bwd_coef_partials(const float* part, int nrows, float* ws, long ws_elems, const float* invstd,
                                 const bf16_t* gamma, long M, int C, bf16_t* dgamma, bf16_t* dbeta, float* coef,
                                 int acc_params, hipStream_t st) {
-    if (merged_finalize(nrows, C) && (fin_slices(nrows) == 1 || (ws && ws_elems >= (long)fin_slices(nrows) * 2 * C))) {
+    if (merged_finalize(C) && (fin_slices(nrows) == 1 || (ws && ws_elems >= (long)fin_slices(nrows) * 2 * C))) {
         bwd_finalize<bf16_t>(part, nrows, fin_slices(nrows) == 1 ? nullptr : ws, C, M, gamma, invstd, dgamma, dbeta,
                              coef, acc_params, st);
         return 0;

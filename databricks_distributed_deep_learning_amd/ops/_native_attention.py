@@ -7,7 +7,6 @@ ViT-B/16); other head dims use the reference path.
 from __future__ import annotations
 
 import math
-import os
 
 import torch
 
@@ -21,12 +20,8 @@ _lib.register({
     "ddl_attn_dmask_words": [I, I, I],
 })
 
-# the fused backward (S <= 128) also writes per-batch column sums of dQKV, from which the QKV
-# Linear takes its bias gradient instead of another pass over dQKV (DDL_ATTN_COLSUM=0: off)
-_COLSUM = os.environ.get("DDL_ATTN_COLSUM", "1") != "0"
-# measurement only (never a training setting): DDL_ATTN_NODROP_DEBUG=1 drops the attention-
-# probability dropout, to price its in-kernel mask generation in an A/B run
-_NODROP_DEBUG = os.environ.get("DDL_ATTN_NODROP_DEBUG", "0") == "1"
+# the backward also writes column sums of dQKV, from which the QKV Linear takes its bias gradient
+# instead of another pass over dQKV
 
 
 class _Attention(torch.autograd.Function):
@@ -64,16 +59,15 @@ class _Attention(torch.autograd.Function):
         # QKV bias gradient rows: per batch (single-workgroup kernels) or per batch and 16-row group
         # (tiled backward kernels: 64-row workgroups of 4 waves)
         tiled_rows = B * 4 * -(-S // 64)
-        cs = torch.empty(tiled_rows, 3 * H * 64, dtype=torch.float32, device=qkv.device) if _COLSUM else None
+        cs = torch.empty(tiled_rows, 3 * H * 64, dtype=torch.float32, device=qkv.device)
         rc = _lib.fn("ddl_attn_bwd")(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), _lib.p(m),
                                      delta.data_ptr(), dqkv.data_ptr(), B, S, H, scale, p_drop, _lib.p(dmask),
                                      _lib.p(cs), _lib.stream())
         if rc not in (0, 2):
             raise RuntimeError(f"native kernel ddl_attn_bwd failed with HIP error {rc}")
-        if cs is not None:
-            # rides on the gradient: the producing Linear's bias gradient = column sums of these rows
-            # (the version guards against autograd accumulating another gradient into dqkv)
-            dqkv._ddl_colsum_rows = (cs[:tiled_rows] if rc == 2 else cs[:B], dqkv._version)
+        # rides on the gradient: the producing Linear's bias gradient = column sums of these rows
+        # (the version guards against autograd accumulating another gradient into dqkv)
+        dqkv._ddl_colsum_rows = (cs[:tiled_rows] if rc == 2 else cs[:B], dqkv._version)
         return dqkv, None, None, None
 
 
@@ -82,4 +76,4 @@ def attention(qkv, num_heads, mask, dropout_p):
     if qkv.dtype != torch.bfloat16 or three_hd != 3 * 64 * num_heads:
         from .attention import attention_reference
         return attention_reference(qkv, num_heads, mask, dropout_p, dropout_p > 0)
-    return _Attention.apply(qkv, num_heads, mask, 0.0 if _NODROP_DEBUG else float(dropout_p))
+    return _Attention.apply(qkv, num_heads, mask, float(dropout_p))

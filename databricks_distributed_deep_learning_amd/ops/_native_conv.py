@@ -32,7 +32,6 @@ def _desc(N, H, W, C, P, Q, stride, h_off, w_off, h_step, w_step, R, S, OH, OW, 
 
 
 STATS_MIN_K = int(os.environ.get("DDL_BN_STATS_MIN_K", "0"))
-STATS_EPILOGUE = os.environ.get("DDL_BN_STATS_EPI", "1") != "0"   # 0: always a separate statistics pass
 _DGRAD_NT = os.environ.get("DDL_DGRAD_NT", "1") != "0"
 
 
@@ -72,21 +71,15 @@ def _direct3x3(x, w, y, part=None, res=None, bnb=None, grid=0):
     return rc
 
 
-_SKINNY = os.environ.get("DDL_SKINNY", "1") != "0"
-_SKINNY_RESBNB = os.environ.get("DDL_SKINNY_RESBNB", "1") != "0"
-
-
-_STREAM = os.environ.get("DDL_STREAM_GEMM", "1") != "0"
 # (N, K) the streaming kernel takes: ResNet stage 2 (B whole in registers) and stage 3's wide output
-# (B in 256-column slabs over workgroups that share their A rows in one XCD's L2); DDL_STREAM_GEMM=2:
-# stage 2 only.  (256, 1024) is covered by the kernel (128-column slabs) but measured no faster than
+# (B in 256-column slabs over workgroups that share their A rows in one XCD's L2).
+# (256, 1024) is covered by the kernel (128-column slabs) but measured no faster than
 # the 256x256 kernel (benchmarks/stream_bench.py: 45 vs 36 us with statistics, 51 vs 52 with the
 # BN-backward epilogue: its A operand is the 103 MB side and two slabs read it twice)
 # (256, 1024) -- stage 3's conv1 input gradient with the BN-backward epilogue only (forward with
 # statistics stays on the general GEMMs): ResNet-50 same-box backward 14.58 vs 14.63-14.64 ms (11,723-
-# 11,739 img/s; DDL_STREAM_GEMM=2, stage 2 only: 11,488-11,506)
-_STREAM_SHAPES = ((512, 128), (128, 512)) + (((1024, 256), (256, 1024)) if os.environ.get("DDL_STREAM_GEMM", "1")
-                                             != "2" else ())
+# 11,739 img/s; with stage 2 only: 11,488-11,506)
+_STREAM_SHAPES = ((512, 128), (128, 512), (1024, 256), (256, 1024))
 
 
 def _stream(a, b, c, part=None, res=None, bnb=None):
@@ -95,7 +88,7 @@ def _stream(a, b, c, part=None, res=None, bnb=None):
     (256, 1024), bf16, contiguous; a residual only together with the BN-backward epilogue (N = 512
     / 1024).  Returns the statistics rows
     written, or None when not covered (nothing launched)."""
-    if not (_STREAM and a.is_cuda):
+    if not a.is_cuda:
         return None
     M, K = a.shape
     N = b.shape[0]
@@ -128,7 +121,7 @@ def _skinny(a, b, c, part=None, res=None, bnb=None):
     for N = 256, BN-backward epilogue for N = 64, or for N = 256 together with the residual.
     Stage-2 shapes go to the register-B kernel (``_stream``).
     Returns the statistics rows written, or None when not covered (nothing launched)."""
-    if not (_SKINNY and a.is_cuda):
+    if not a.is_cuda:
         return None
     M, K = a.shape
     N = b.shape[0]
@@ -139,7 +132,7 @@ def _skinny(a, b, c, part=None, res=None, bnb=None):
     ts = [a, b, c] + ([res] if res is not None else []) + ([bnb.x] if bnb is not None else [])
     if any(t.dtype != torch.bfloat16 or not t.is_contiguous() for t in ts):
         return None
-    if (res is not None and N != 256) or (bnb is not None and N != 64 and (res is None or not _SKINNY_RESBNB)):
+    if (res is not None and N != 256) or (bnb is not None and N != 64 and res is None):
         return None
     if res is not None and tuple(res.shape) != (M, N) or bnb is not None and bnb.x.numel() != M * N:
         return None
@@ -167,7 +160,7 @@ def _fwd(x, w, stride, pad, bias=None, act=None, residual=None, stats=None):
     if (bias is None and act is None and residual is None and x.is_cuda
             and _direct3x3_ok(x.shape, w.shape, stride, pad)):
         y = torch.empty(N, H, W_, K, dtype=x.dtype, device=x.device)
-        use_stats = STATS_EPILOGUE and stats is not None
+        use_stats = stats is not None
         part = torch.empty(_direct3x3_rows(N * H * W_) * 2 * K, dtype=torch.float32, device=x.device) \
             if use_stats else None
         r = _direct3x3(x, w, y, part)
@@ -182,7 +175,7 @@ def _fwd(x, w, stride, pad, bias=None, act=None, residual=None, stats=None):
     kernel = None
     plain11 = R == 1 and S == 1 and stride == 1 and pad == 0
     desc = None if plain11 else _desc(N, H, W_, C, P, Q, stride, -pad, -pad, 1, 1, R, S, P, Q)
-    if STATS_EPILOGUE and stats is not None and bias is None and act is None and residual is None and x.is_cuda:
+    if stats is not None and bias is None and act is None and residual is None and x.is_cuda:
         # BatchNorm statistics from the GEMM epilogue instead of a separate read pass
         # over y: nearly free in the 256x256 kernel's register epilogue and, since the
         # 128-row kernels reduce with DPP row sums too, on every tuned kernel
@@ -269,15 +262,12 @@ class _WDgradCache:
         return job[3]
 
 
-_WDG_BATCH = os.environ.get("DDL_WDG_BATCH", "1") != "0"
-
-
 def _w_dgrad(w, rs, ss, param=None):
     """[C, len(rs), len(ss), K] = w[:, rs][:, :, ss] transposed.  With ``param`` (the
     arena parameter ``w`` is) the layout comes from the arena's per-step batch."""
     ref = getattr(param, "_ddl_arena", None) if param is not None else None
     arena = ref() if ref is not None else None
-    if _WDG_BATCH and arena is not None and param.data_ptr() == w.data_ptr() and w.is_cuda \
+    if arena is not None and param.data_ptr() == w.data_ptr() and w.is_cuda \
             and not torch.cuda.is_current_stream_capturing():
         cache = getattr(arena, "_ddl_wdg", None)
         if cache is None:
@@ -655,12 +645,9 @@ def _s2d_weight_grad(dws, w_shape):
     return d[:, :R, :S, :C]
 
 
-_STEM_WGRAD = os.environ.get("DDL_STEM_WGRAD", "1") != "0"
-
-
 def _stem_wgrad_ok(xs, dy, ws_shape, w_shape) -> bool:
     """Shapes the direct stem weight-gradient kernel (stem_wgrad.hip) covers."""
-    if not (_STEM_WGRAD and xs.is_cuda and dy.is_cuda):
+    if not (xs.is_cuda and dy.is_cuda):
         return False
     N, Hx, Wx, Cs = xs.shape
     _, P, Q, K = dy.shape
@@ -687,13 +674,10 @@ def _stem_wgrad(xs, dy, dw, accumulate, grid=0):
     return dw
 
 
-_STEM_FWD = os.environ.get("DDL_STEM_FWD", "1") != "0"
-
-
 def _stem_fwd_ok(xs, ws) -> bool:
     """Shapes the direct stem forward kernel (stem_conv.hip) covers: output P x Q with P % 4 == 0,
     Q % 16 == 0, 16 <= Q <= 112, 64 channels."""
-    if not (_STEM_FWD and xs.is_cuda):
+    if not xs.is_cuda:
         return False
     N, Hx, Wx, Cs = xs.shape
     P, Q = Hx - 3, Wx - 3
@@ -708,7 +692,7 @@ def _stem_fwd(xs, ws, stats=None, grid=0):
     N, Hx, Wx, _ = xs.shape
     P, Q = Hx - 3, Wx - 3
     y = torch.empty(N, P, Q, 64, dtype=xs.dtype, device=xs.device)
-    use_stats = STATS_EPILOGUE and stats is not None
+    use_stats = stats is not None
     g = grid if grid > 0 else 256
     part = torch.empty(g * 2 * 64, dtype=torch.float32, device=xs.device) if use_stats else None
     rc = _lib.fn("ddl_stem_fwd")(xs.data_ptr(), ws.data_ptr(), y.data_ptr(), N, P, Q, 64, _lib.p(part), int(grid),
@@ -769,9 +753,6 @@ class _StemConvS2D(torch.autograd.Function):
             else:
                 dw = g.contiguous()
         return None, dw, None, None
-
-
-_STEM_S2D = os.environ.get("DDL_STEM_S2D", "1") != "0"
 
 
 class _PatchEmbed(torch.autograd.Function):
@@ -837,7 +818,7 @@ def conv2d(x, w, stride, padding, bridge=None, stats=None, grad_to=None):
     from .bridge import join
     from .conv import conv2d_reference
     C = x.shape[-1]
-    if (_STEM_S2D and stride == 2 and C <= 4 and w.shape[1] % 2 == 1 and w.shape[2] % 2 == 1 and
+    if (stride == 2 and C <= 4 and w.shape[1] % 2 == 1 and w.shape[2] % 2 == 1 and
             x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and w.shape[0] % 8 == 0 and
             not x.requires_grad and bridge is None):
         return _StemConvS2D.apply(x, w, padding, stats)

@@ -21,11 +21,6 @@ _BN_BWD_EPI = os.environ.get("DDL_BN_BWD_EPI", "1") != "0"
 _BN_BWD_EPI_RES = os.environ.get("DDL_BN_BWD_EPI", "1") not in ("0", "nores")
 
 
-# LayerNorm backward adds its input gradient's column sums (the producing Linear's bias
-# gradient) straight into that bias's arena slot (DDL_LN_BIAS_SINK=0: the Linear adds them)
-_LN_BIAS_SINK = os.environ.get("DDL_LN_BIAS_SINK", "1") != "0"
-
-
 def _bn_supported(C: int) -> bool:
     return C % 8 == 0 and 256 % (C // 8) == 0
 
@@ -310,7 +305,7 @@ class _BNReluMaxPoolTrain(torch.autograd.Function):
 def bn_relu_maxpool(x, weight, bias, running_mean, running_var, momentum, eps, pre=None):
     """Training maxpool3x3/2/pad1(relu(BN(x))) in one pass; None when not covered."""
     N, H, W, C = x.shape
-    if (not _FUSED_STEM or not _bn_supported(C) or x.dtype not in (torch.bfloat16, torch.float32)
+    if (not _bn_supported(C) or x.dtype not in (torch.bfloat16, torch.float32)
             or H % 2 or W % 2 or weight is None):
         return None
     if weight.dtype != x.dtype:
@@ -318,20 +313,18 @@ def bn_relu_maxpool(x, weight, bias, running_mean, running_var, momentum, eps, p
     return _BNReluMaxPoolTrain.apply(x, weight, bias, running_mean, running_var, momentum, eps, pre)
 
 
-_FUSED_STEM = os.environ.get("DDL_FUSED_STEM", "1") != "0"
 # backward of the fused stem with the max-pool gather inside the BN backward passes: saves the
 # activation-gradient write but the gathers slow both passes about as much (same-box A/B neutral
 # within noise), so the default keeps max-pool backward + BN backward
 _FUSED_STEM_BWD = os.environ.get("DDL_FUSED_STEM_BWD", "0") != "0"
-_DUAL_BN = os.environ.get("DDL_DUAL_BN", "1") != "0"
 
 
 def batch_norm_add_bn(x, weight, bias, running_mean, running_var, momentum, eps, x2, weight2, bias2,
                       running_mean2, running_var2, momentum2, eps2, pre=None, pre2=None):
     """Training relu(BN(x) + BN2(x2)) in one apply pass; None when not covered (the caller
-    then runs the two BatchNorms separately; DDL_DUAL_BN=0 always)."""
+    then runs the two BatchNorms separately)."""
     C = x.shape[-1]
-    if (not _DUAL_BN or not _bn_supported(C) or x.dtype not in (torch.bfloat16, torch.float32) or x2.dtype != x.dtype
+    if (not _bn_supported(C) or x.dtype not in (torch.bfloat16, torch.float32) or x2.dtype != x.dtype
             or x2.shape != x.shape or weight is None or weight2 is None):
         return None
     if weight.dtype != x.dtype:
@@ -383,8 +376,9 @@ def batch_norm(x, weight, bias, running_mean, running_var, training, momentum, e
 class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps, residual, drop_p, bridge=None, grad_from=None):
-        # the bias of the Linear that produced x
-        ctx.bias_param = getattr(x, "_ddl_bias_param", None) if _LN_BIAS_SINK else None
+        # the bias of the Linear that produced x: the backward adds its input gradient's column sums
+        # (that bias's gradient) straight into its arena slot
+        ctx.bias_param = getattr(x, "_ddl_bias_param", None)
         ctx.grad_from = grad_from
         x = x.contiguous()
         H = x.shape[-1]

@@ -28,28 +28,32 @@ def emit(src: str, out: str, defines) -> None:
     subprocess.run(cmd, check=True)
 
 
+def loop_spills(lines):
+    """(MFMAs, scratch instructions, scratch instructions inside the MFMA main loop) of one kernel body."""
+    mf = [i for i, ln in enumerate(lines) if "v_mfma" in ln]
+    sc = [i for i, ln in enumerate(lines) if "scratch_" in ln]
+    loop = 0
+    if mf:
+        # MFMA clusters: runs of v_mfma lines less than 400 lines apart; the main loop is the largest
+        clusters, a, prev = [], mf[0], mf[0]
+        for i in mf[1:]:
+            if i - prev > 400:
+                clusters.append((a, prev))
+                a = i
+            prev = i
+        clusters.append((a, prev))
+        lo, hi = max(clusters, key=lambda c: sum(1 for x in mf if c[0] <= x <= c[1]))
+        loop = sum(1 for i in sc if lo <= i <= hi)
+    return len(mf), len(sc), loop
+
+
 def scan(text: str):
     rows = []
     for m in PAT.finditer(text):
         name, body = m.group(1), m.group(2)
         t = TPL.search(name)
         tag = "".join(t.groups()) if t else "wg" if "gemm_wg_k" in name else name[-40:]
-        lines = body.split("\n")
-        mf = [i for i, ln in enumerate(lines) if "v_mfma" in ln]
-        sc = [i for i, ln in enumerate(lines) if "scratch_" in ln]
-        loop = 0
-        if mf:
-            # MFMA clusters: runs of v_mfma lines less than 400 lines apart; the main loop is the largest
-            clusters, a, prev = [], mf[0], mf[0]
-            for i in mf[1:]:
-                if i - prev > 400:
-                    clusters.append((a, prev))
-                    a = i
-                prev = i
-            clusters.append((a, prev))
-            lo, hi = max(clusters, key=lambda c: sum(1 for x in mf if c[0] <= x <= c[1]))
-            loop = sum(1 for i in sc if lo <= i <= hi)
-        rows.append((tag, len(mf), len(sc), loop))
+        rows.append((tag, *loop_spills(body.split("\n"))))
     return rows
 
 

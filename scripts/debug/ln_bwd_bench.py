@@ -1,5 +1,5 @@
 """Time the LayerNorm backward (BERT-base shape, fused post-LN dropout) in isolation:
-``python scripts/debug/ln_bwd_bench.py`` (grid knobs: DDL_LN_BWD_ROWS / DDL_LN_BWD_MAXBLK)."""
+``python scripts/debug/ln_bwd_bench.py``."""
 import os
 import sys
 
@@ -29,8 +29,7 @@ def main():
         y.backward(g)
     e1.record()
     torch.cuda.synchronize()
-    print(f"rows/blk={os.environ.get('DDL_LN_BWD_ROWS', '32')} cap={os.environ.get('DDL_LN_BWD_MAXBLK', '1024')} "
-          f"ln backward {e0.elapsed_time(e1) / n * 1000:.1f} us")
+    print(f"ln backward {e0.elapsed_time(e1) / n * 1000:.1f} us")
 
 
 if __name__ == "__main__":

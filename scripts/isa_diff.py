@@ -9,6 +9,11 @@ from REV_A's csrc/ and once from REV_B's (default: the working tree); revisions 
 source (.file, .ident, comments, the per-compile __hip_cuid_ symbol) are dropped; the rest must be
 equal line for line.  Prints one markdown table row per file and, for a file that differs, the
 kernel holding the first difference and that hunk.  Exit status 1 if any file differs.
+
+--per-kernel gives one row per kernel instead: its body after normalising block labels and symbol
+suffixes (identical / differs / removed / added), and parent / new VGPRs, SGPRs, scratch bytes, LDS
+bytes, the scripts/check_spills.py count of scratch instructions in the MFMA main loop, and the waves
+per SIMD the registers and the LDS allow.  Exit status 1 if a kept kernel's figure got worse.
 """
 from __future__ import annotations
 
@@ -24,6 +29,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from check_spills import loop_spills  # noqa: E402
 from isa_census import compile_asm  # noqa: E402
 
 
@@ -61,12 +67,72 @@ def first_hunk(a, b):
     return None, []
 
 
+META = {"vgpr": "vgpr_count", "sgpr": "sgpr_count", "scratch": "private_segment_fixed_size",
+        "lds": "group_segment_fixed_size", "wg": "max_flat_workgroup_size"}
+
+
+def kernel_table(lines):
+    """{demangled kernel name: (normalised body lines, figures)} of one file's assembly."""
+    meta, name, cur = {}, None, {}
+    for l in lines:     # a kernel's metadata entry: keys in alphabetical order, .vgpr_count the last one read
+        if (m := re.match(r"\s+(?:- )?\.name:\s+(_Z\S+)", l)):
+            name = m.group(1)
+        for k, f in META.items():
+            if (m := re.match(r"\s+(?:- )?\." + f + r":\s+(\d+)", l)):
+                cur[k] = int(m.group(1))
+                if k == "vgpr":
+                    meta[name], cur = cur, {}
+    out = {}
+    for i, l in enumerate(lines):
+        if not (m := re.match(r"^(_Z\S+):", l)) or m.group(1) not in meta:
+            continue
+        j = next(k for k in range(i, len(lines)) if lines[k].strip().startswith(".Lfunc_end"))
+        # block labels carry the function's index in the file, symbols a per-compile hash
+        # (also in the trailing "; in Loop: Header=BB126_15" comments, which go)
+        body = [re.sub(r"\.L(BB|tmp|func_\w+?)\d+(_\d+)?", r".L\1\2", x.split(";")[0].rstrip()) for x in lines[i + 1:j]]
+        f = dict(meta[m.group(1)])
+        f["loop"] = loop_spills(body)[2] if any("v_mfma" in x for x in body) else None
+        # gfx950: 512 unified registers per SIMD lane in granules of 8, 160 KB of LDS per CU, 4 SIMDs
+        by_lds = (163840 // f["lds"]) * (f["wg"] // 64) // 4 if f.get("lds") else 8
+        f["waves"] = max(0, min(8, 512 // (-(-max(f["vgpr"], 1) // 8) * 8), by_lds))
+        short = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
+        out[re.sub(r"\(anonymous namespace\)::", "", short).split("(")[0]] = (body, f)
+    return out
+
+
+def per_kernel(names, fa, fb) -> int:
+    worse = 0
+    print("| file | kernel | body | VGPR p/n | SGPR p/n | scratch B p/n | LDS p/n | loop spills p/n | waves/SIMD p/n |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for n in names:
+        ka, kb = kernel_table(fa[n].result() or []), kernel_table(fb[n].result() or [])
+        for k in sorted(set(ka) | set(kb)):
+            (x, p), (y, q) = ka.get(k, (None, {})), kb.get(k, (None, {}))
+            if x is None or y is None:
+                body = "added" if x is None else "REMOVED"
+            elif x == y:
+                body = "identical"
+            else:
+                nd = sum(max(i1 - i0, j1 - j0) for t, i0, i1, j0, j1 in
+                         difflib.SequenceMatcher(None, x, y, autojunk=False).get_opcodes() if t != "equal")
+                body = f"differs ({nd} of {len(x)} lines)"
+            def show(key):
+                return "/".join("-" if d.get(key) is None else str(d[key]) for d in (p, q) if d)
+            if p and q:
+                worse += any((q[f] or 0) > (p[f] or 0) for f in ("vgpr", "sgpr", "scratch", "lds", "loop"))
+                worse += q["waves"] < p["waves"]
+            print(f"| `{n}` | `{k}` | {body} | " + " | ".join(show(f) for f in
+                  ("vgpr", "sgpr", "scratch", "lds", "loop", "waves")) + " |")
+    return 1 if worse else 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("rev_a")
     ap.add_argument("rev_b", nargs="?", default=None)
     ap.add_argument("-j", "--jobs", type=int, default=8)
     ap.add_argument("--only", default=".", metavar="REGEX", help="compare only the files whose name matches")
+    ap.add_argument("--per-kernel", action="store_true", help="one row per kernel, with its resource figures")
     a = ap.parse_args()
     bad, hunks = 0, []
     with tempfile.TemporaryDirectory() as tmp:
@@ -76,6 +142,8 @@ def main() -> int:
         with cf.ThreadPoolExecutor(max_workers=max(1, a.jobs)) as ex:
             fa = {n: ex.submit(asm_lines, ca, n, tmp) for n in names}
             fb = {n: ex.submit(asm_lines, cb, n, tmp) for n in names}
+            if a.per_kernel:
+                return per_kernel(names, fa, fb)
             print(f"| file | asm lines {a.rev_a} | asm lines {a.rev_b or 'working tree'} | verdict |")
             print("|---|---:|---:|---|")
             for n in names:
