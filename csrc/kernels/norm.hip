@@ -1,7 +1,7 @@
 // BatchNorm (NHWC, channels innermost) and LayerNorm kernels for gfx950.
 //
 // BatchNorm training forward = 3 launches:
-//   bn_stats_partial  : per-block per-channel (sum, sumsq), 16-byte loads
+//   bn_stats_partial  : per-block per-channel (sum, sum of squares about a pivot), 16-byte loads
 //   bn_stats_finalize : merge partials in fp64, mean/invstd, running-stat update,
 //                       fold gamma/beta into per-channel (scale, shift)
 //   bn_apply          : y = x*scale + shift (+ residual) (ReLU), one pass
@@ -23,7 +23,14 @@ constexpr int BN_NT = 256;
 // ------------------------------------------------------------------ BN stats
 template <typename T>
 __global__ __launch_bounds__(BN_NT) void bn_stats_partial_k(const T* __restrict__ x, long M, int C,
-                                                            int rows_per_blk, float* __restrict__ part) {
+                                                            int rows_per_blk, float* __restrict__ part,
+                                                            const T* __restrict__ pivot = nullptr, int prows = 0) {
+    // pivot (nullable: prows rows of C values from the data, here the first rows of x; their mean
+    // k is the pivot): the squares are taken of x - k, so that var = E[(x - k)^2] - (mean - k)^2
+    // cancels at (mean - k)^2 / var and not at mean^2 / var -- at mean / std = 8 one block's fp32 sum
+    // of squares alone cost var 4e-6 relative.  (One row would do there, but for centred data it is
+    // the worse pivot than 0 by its own (x0 - mean)^2 / var.)  The plain sum stays plain: about a
+    // pivot it would be the larger one for centred data.
     __shared__ float s_red[2 * BN_NT * 8];
     const int tpr = C / 8;            // threads per row (each owns 8 channels)
     const int rpi = BN_NT / tpr;      // rows per iteration
@@ -31,9 +38,20 @@ __global__ __launch_bounds__(BN_NT) void bn_stats_partial_k(const T* __restrict_
     const int cg = tid % tpr, rr = tid / tpr;
     const long r0 = (long)blockIdx.x * rows_per_blk;
     const long r1 = min(M, r0 + rows_per_blk);
-    float s[8], q[8];
+    float s[8], q[8], kp[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; }
+    for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; kp[j] = 0.f; }
+    if (pivot) {
+        for (int i = 0; i < prows; ++i) {
+            float v[8];
+            load8(pivot + (long)i * C + cg * 8, v);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) kp[j] += v[j];
+        }
+        const float inv = 1.f / (float)prows;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) kp[j] *= inv;
+    }
     long r = r0 + rr;
     for (; r + 3 * rpi < r1; r += 4 * rpi) {   // 4 rows of 16-byte loads in flight
         float v[4][8];
@@ -42,13 +60,13 @@ __global__ __launch_bounds__(BN_NT) void bn_stats_partial_k(const T* __restrict_
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { s[j] += v[u][j]; q[j] += v[u][j] * v[u][j]; }
+            for (int j = 0; j < 8; ++j) { const float d = v[u][j] - kp[j]; s[j] += v[u][j]; q[j] += d * d; }
     }
     for (; r < r1; r += rpi) {
         float v[8];
         load8(x + r * C + cg * 8, v);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { s[j] += v[j]; q[j] += v[j] * v[j]; }
+        for (int j = 0; j < 8; ++j) { const float d = v[j] - kp[j]; s[j] += v[j]; q[j] += d * d; }
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -67,16 +85,19 @@ __global__ __launch_bounds__(BN_NT) void bn_stats_partial_k(const T* __restrict_
     }
 }
 
-// channel c's statistics from its summed [sum | sumsq]: mean / invstd saved, running stats
-// updated, gamma / beta folded into (scale, shift)
+// channel c's statistics from its summed [sum of x | sum of (x - k)^2] (k: the pivot the squares
+// were taken about, 0 for plain squares): mean / invstd saved, running stats updated, gamma / beta folded into
+// (scale, shift)
 template <typename TP>
 __device__ __forceinline__ void bn_fwd_finish_channel(int c, double s, double q, long M, const TP* __restrict__ gamma,
                                                       const TP* __restrict__ beta, float* __restrict__ running_mean,
                                                       float* __restrict__ running_var, float momentum, float eps,
                                                       float* __restrict__ save_mean, float* __restrict__ save_invstd,
-                                                      float* __restrict__ scale, float* __restrict__ shift) {
+                                                      float* __restrict__ scale, float* __restrict__ shift,
+                                                      double k = 0.) {
     const double mean = s / (double)M;
-    double var = q / (double)M - mean * mean;
+    const double dk = mean - k;
+    double var = q / (double)M - dk * dk;
     if (var < 0) var = 0;
     const float invstd = (float)(1.0 / sqrt(var + (double)eps));
     save_mean[c] = (float)mean;
@@ -92,19 +113,57 @@ __device__ __forceinline__ void bn_fwd_finish_channel(int c, double s, double q,
     shift[c] = bb - (float)mean * g * invstd;
 }
 
+// colsum64 (ddl_common.h: 64 columns x 16 row groups) accumulated in fp64.  The forward statistics
+// meet in var = E[x^2] - mean^2: every fp32 addition of the blocks' partial rows costs the variance
+// (mean^2 / var) * 2^-24 -- 2e-5 relative at mean / std = 8 over 392 partial rows -- while the
+// partial rows themselves are short sums.  `red` holds 1024 doubles.
+__device__ __forceinline__ double colsum64_f64(const float* __restrict__ part, int nrows, long ld, int col, bool ok,
+                                               double* red) {
+    const int grp = threadIdx.x >> 6;
+    double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;
+    if (ok) {
+        int r = grp;
+        for (; r + 112 < nrows; r += 128) {
+            float v[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = part[(long)(r + 16 * i) * ld + col];
+            a0 += (double)v[0] + (double)v[4];
+            a1 += (double)v[1] + (double)v[5];
+            a2 += (double)v[2] + (double)v[6];
+            a3 += (double)v[3] + (double)v[7];
+        }
+        for (; r < nrows; r += 16) a0 += (double)part[(long)r * ld + col];
+    }
+    red[threadIdx.x] = (a0 + a1) + (a2 + a3);
+    __syncthreads();
+    double s = 0.;
+    if (threadIdx.x < 64) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s += red[i * 64 + threadIdx.x];
+    }
+    __syncthreads();
+    return s;
+}
+
 template <typename TP>
 __global__ __launch_bounds__(1024) void bn_stats_finalize_k(const float* __restrict__ part, int nblk, int C, long M,
                                     const TP* __restrict__ gamma, const TP* __restrict__ beta,
                                     float* __restrict__ running_mean, float* __restrict__ running_var, float momentum,
                                     float eps, float* __restrict__ save_mean, float* __restrict__ save_invstd,
-                                    float* __restrict__ scale, float* __restrict__ shift) {
-    __shared__ float red[1024];
+                                    float* __restrict__ scale, float* __restrict__ shift,
+                                    const TP* __restrict__ pivot = nullptr, int prows = 0) {
+    __shared__ double red[1024];
     const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-    const double s = colsum64(part, nblk, 2L * C, c, c < C, red);
-    const double q = colsum64(part, nblk, 2L * C, C + c, c < C, red);
+    const double s = colsum64_f64(part, nblk, 2L * C, c, c < C, red);
+    const double q = colsum64_f64(part, nblk, 2L * C, C + c, c < C, red);
     if (threadIdx.x >= 64 || c >= C) return;
+    float k = 0.f;                    // the pivot exactly as bn_stats_partial_k forms it
+    if (pivot) {
+        for (int i = 0; i < prows; ++i) k += to_f(pivot[(long)i * C + c]);
+        k *= 1.f / (float)prows;
+    }
     bn_fwd_finish_channel<TP>(c, s, q, M, gamma, beta, running_mean, running_var, momentum, eps, save_mean,
-                              save_invstd, scale, shift);
+                              save_invstd, scale, shift, (double)k);
 }
 
 // eval mode: scale/shift from running statistics
@@ -809,14 +868,17 @@ DDL_API int ddl_bn_fwd_train(int dtype, const void* x, long M, int C, const void
     const int rpi = BN_NT / (C / 8);
     long rpb = (M + nblk - 1) / nblk;
     rpb = (rpb + rpi - 1) / rpi * rpi;
+    const int prows = (int)std::min<long>(M, 8);   // the pivot of the squares: the mean of the first rows
     if (dtype == 1) {
-        bn_stats_partial_k<bf16_t><<<nblk, BN_NT, 0, st>>>((const bf16_t*)x, M, C, (int)rpb, part);
+        bn_stats_partial_k<bf16_t><<<nblk, BN_NT, 0, st>>>((const bf16_t*)x, M, C, (int)rpb, part, (const bf16_t*)x, prows);
         bn_stats_finalize_k<bf16_t><<<(C + 63) / 64, 1024, 0, st>>>(part, nblk, C, M, (const bf16_t*)gamma,
-            (const bf16_t*)beta, running_mean, running_var, momentum, eps, save_mean, save_invstd, scale, shift);
+            (const bf16_t*)beta, running_mean, running_var, momentum, eps, save_mean, save_invstd, scale, shift,
+            (const bf16_t*)x, prows);
     } else {
-        bn_stats_partial_k<float><<<nblk, BN_NT, 0, st>>>((const float*)x, M, C, (int)rpb, part);
+        bn_stats_partial_k<float><<<nblk, BN_NT, 0, st>>>((const float*)x, M, C, (int)rpb, part, (const float*)x, prows);
         bn_stats_finalize_k<float><<<(C + 63) / 64, 1024, 0, st>>>(part, nblk, C, M, (const float*)gamma,
-            (const float*)beta, running_mean, running_var, momentum, eps, save_mean, save_invstd, scale, shift);
+            (const float*)beta, running_mean, running_var, momentum, eps, save_mean, save_invstd, scale, shift,
+            (const float*)x, prows);
     }
     DDL_RETURN_LAUNCH();
 }
