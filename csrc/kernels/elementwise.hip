@@ -198,12 +198,20 @@ __global__ __launch_bounds__(256) void softmax_topk_k(const T* __restrict__ logi
     }
 }
 
+// Summed in fp64: one row loss far above the others (a saturated row: ~2e4 among ~8) puts every partial
+// sum at its magnitude, and each fp32 rounding there cost the mean ulp(2e4) / n (one block over B
+// floats: the wider adds cost nothing measurable).
 __global__ void mean_k(const float* __restrict__ v, long n, float* __restrict__ out) {
-    __shared__ float red[4];
-    float s = 0.f;
-    for (long i = threadIdx.x; i < n; i += 256) s += v[i];
-    s = block_sum<256>(s, red);
-    if (threadIdx.x == 0) out[0] = s / (float)n;
+    __shared__ double red[256];
+    double s = 0.0;
+    for (long i = threadIdx.x; i < n; i += 256) s += (double)v[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = (float)(red[0] / (double)n);
 }
 template <typename T>
 __global__ __launch_bounds__(256) void scale_k(const T* __restrict__ x, const float* __restrict__ s, T* __restrict__ y,
@@ -228,8 +236,11 @@ __global__ __launch_bounds__(256) void maxpool_fwd_k(const T* __restrict__ x, T*
         const int n = (int)(t / P);
         float best[8];
         uint8_t arg[8];
+        // the recorded tap starts at the first IN-BOUNDS tap: a window whose in-bounds values are all
+        // -inf keeps it, and tap 0 of a border window is a padding position the backward never matches
+        const uint8_t arg0 = (uint8_t)(max(0, pad - p * S) * K + max(0, pad - q * S));
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { best[j] = -INFINITY; arg[j] = 0; }
+        for (int j = 0; j < 8; ++j) { best[j] = -INFINITY; arg[j] = arg0; }
         for (int r = 0; r < K; ++r) {
             const int h = p * S - pad + r;
             if (h < 0 || h >= H) continue;
