@@ -422,7 +422,10 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_wgrad_k(C3WParams p) {
                 for (int i = tid; i < 8192 / 16; i += NT)
                     reinterpret_cast<uint4*>(smem + NSLOT * ROWB + buf * DYB + 8192)[i] = make_uint4(0u, 0u, 0u, 0u);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // lgkmcnt too: the plain LDS stores that clear an odd H's missing dy row (just above, or in the
+        // previous tile's prefetch) must have landed before another wave reads them; a bare s_barrier
+        // does not wait for them
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         // prefetch the next tile: its two new x rows and its dy rows (other dy image; a
         // missing second row -- odd H -- is cleared instead)
