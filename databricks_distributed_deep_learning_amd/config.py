@@ -83,7 +83,7 @@ class TrainConfig:
     def resolved_task(self) -> str:
         if self.task != "auto":
             return self.task
-        return "nlp" if self.model.startswith("bert") else "cv"
+        return "nlp" if self.model.startswith(("bert", "gpt")) else "cv"
 
     @property
     def resolved_optimizer(self) -> str:
@@ -91,7 +91,7 @@ class TrainConfig:
             return self.optimizer
         if self.model.startswith("bert_large"):
             return "lamb"
-        if self.model.startswith(("bert", "vit")):
+        if self.model.startswith(("bert", "vit", "gpt")):
             return "adamw"
         return "sgd"
 
@@ -175,6 +175,10 @@ PRESETS: Dict[str, TrainConfig] = {
     "bert_large_pretrain": TrainConfig(model="bert_large_pretraining", batch_size=0, seq_len=512, num_classes=2,
                                        mlm_predictions=76, grad_accum=4, dtype="bf16", optimizer="lamb", lr=2e-3,
                                        weight_decay=0.01, dropout=0.1),
+    # GPT-2 small causal-LM pretraining at its full context (16 x 1024 tokens per GPU and step)
+    "gpt2_pretrain": TrainConfig(model="gpt2", batch_size=16, seq_len=1024, vocab_size=50257, dtype="bf16",
+                                 optimizer="adamw", lr=6e-4, weight_decay=0.1, betas=[0.9, 0.95], eps=1e-8,
+                                 dropout=0.1),
 }
 
 

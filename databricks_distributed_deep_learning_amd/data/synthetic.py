@@ -70,12 +70,18 @@ class SyntheticImageNet:
 class SyntheticTokens:
     def __init__(self, batch_size: int, seq_len: int = 128, vocab_size: int = 30522, num_labels: int = 2,
                  device: Optional[torch.device] = None, rank: int = 0, seed: int = 1234, pool: int = 4,
-                 pad_fraction: float = 0.0, steps_per_epoch: int = 0, mlm_predictions: int = 0):
+                 pad_fraction: float = 0.0, steps_per_epoch: int = 0, mlm_predictions: int = 0,
+                 causal_lm: bool = False):
         """``mlm_predictions`` = P > 0 adds the masked-LM pretraining targets to every batch:
         ``masked_lm_positions [B, P]`` (unique per row, ascending, inside the row's unpadded length),
         ``masked_lm_labels [B, P]`` (a random number of trailing slots per row is padding: label
         -100, position 0; at least one slot per row is a target) and ``next_sentence_label [B]``.
-        With 0 the batches are exactly those of a loader without the argument."""
+        With 0 the batches are exactly those of a loader without the argument.
+
+        ``causal_lm`` replaces ``labels`` by the next-token targets ``[B, S]``: ``labels[b, s]`` is
+        ``input_ids[b, s + 1]``, -100 at the last position and wherever position ``s + 1`` is padding
+        (the shift happens here, not in the model).  It draws nothing, so ids and masks are those of
+        a loader without it."""
         self.batch_size, self.seq_len = batch_size, seq_len
         self.device = device or torch.device("cpu")
         self.steps_per_epoch = steps_per_epoch
@@ -89,6 +95,9 @@ class SyntheticTokens:
                                      generator=g, device=self.device)
                 mask = (torch.arange(seq_len, device=self.device)[None, :] < lens[:, None]).to(torch.int64)
             labels = torch.randint(0, num_labels, (batch_size,), generator=g, device=self.device)
+            if causal_lm:
+                labels = torch.full_like(ids, -100)
+                labels[:, :-1] = ids[:, 1:] if mask is None else ids[:, 1:].masked_fill(mask[:, 1:] == 0, -100)
             batch = {"input_ids": ids, "attention_mask": mask, "labels": labels}
             if mlm_predictions > 0:
                 batch.update(self._mlm_targets(mlm_predictions, mask, vocab_size, pad_fraction, g))

@@ -1,4 +1,5 @@
-"""Model zoo (N11): ResNet-18/34/50/101/152, BERT-base/large (+ a tiny test size), ViT-B/16."""
+"""Model zoo (N11): ResNet-18/34/50/101/152, BERT-base/large (+ a tiny test size), ViT-B/16,
+GPT-2 small/medium/large (+ a tiny test size)."""
 from __future__ import annotations
 
 import torch.nn as nn
@@ -7,6 +8,7 @@ from .resnet import ResNet, resnet18, resnet34, resnet50, resnet101, resnet152  
 from .bert import BertConfig, BertForSequenceClassification, bert_base, bert_large, bert_tiny  # noqa: F401
 from .bert import BertForPreTraining, bert_base_pretraining, bert_large_pretraining, bert_tiny_pretraining  # noqa: F401
 from .vit import ViTConfig, ViTForImageClassification, vit_b16  # noqa: F401
+from .gpt2 import GPT2Config, GPT2LMHeadModel, gpt2, gpt2_medium, gpt2_large, gpt2_tiny  # noqa: F401
 from .layers import cast_params, convert_sync_batchnorm  # noqa: F401
 
 _REGISTRY = {
@@ -16,6 +18,7 @@ _REGISTRY = {
     "bert_base_pretraining": bert_base_pretraining, "bert_large_pretraining": bert_large_pretraining,
     "bert_tiny_pretraining": bert_tiny_pretraining,
     "vit_b16": vit_b16,
+    "gpt2": gpt2, "gpt2_medium": gpt2_medium, "gpt2_large": gpt2_large, "gpt2_tiny": gpt2_tiny,
 }
 
 
@@ -30,6 +33,8 @@ def build_model(name: str, num_classes: int = 1000, dropout: float = 0.1, image_
         return _REGISTRY[name](dropout=dropout)      # MLM + NSP heads: no label count
     if name.startswith("bert"):
         return _REGISTRY[name](num_labels=num_classes, dropout=dropout)
+    if name.startswith("gpt"):
+        return _REGISTRY[name](dropout=dropout)           # causal LM: no label count
     if name.startswith("vit"):
         return _REGISTRY[name](num_classes=num_classes, dropout=dropout, image_size=image_size)
     return _REGISTRY[name](num_classes=num_classes)

@@ -18,6 +18,9 @@ _lib.register({
     "ddl_attn_fwd": [P, P, P, P, I, I, I, CF, CF, U64, P, P],
     "ddl_attn_bwd": [P, P, P, P, P, P, P, I, I, I, CF, CF, P, P, P],
     "ddl_attn_dmask_words": [I, I, I],
+    # causal (query i attends to keys j <= i): the tiled kernels' CAUSAL instances for every S
+    "ddl_attn_causal_fwd": [P, P, P, P, I, I, I, CF, CF, U64, P, P],
+    "ddl_attn_causal_bwd": [P, P, P, P, P, P, P, I, I, I, CF, CF, P, P, P],
 })
 
 # the backward also writes column sums of dQKV, from which the QKV Linear takes its bias gradient
@@ -26,7 +29,7 @@ _lib.register({
 
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, num_heads, mask, p_drop):
+    def forward(ctx, qkv, num_heads, mask, p_drop, causal=False):
         qkv = qkv.contiguous()
         B, S, three_hd = qkv.shape
         H = num_heads
@@ -43,16 +46,16 @@ class _Attention(torch.autograd.Function):
             fn = _lib.fn("ddl_attn_dmask_words")
             fn.restype = L
             dmask = torch.empty(fn(B, S, H), dtype=torch.int32, device=qkv.device)
-        _lib.call("ddl_attn_fwd", qkv.data_ptr(), _lib.p(m), out.data_ptr(), lse.data_ptr(), B, S, H, scale,
+        _lib.call("ddl_attn_causal_fwd" if causal else "ddl_attn_fwd", qkv.data_ptr(), _lib.p(m), out.data_ptr(), lse.data_ptr(), B, S, H, scale,
                   float(p_drop), seed, _lib.p(dmask))
-        ctx.meta = (B, S, H, scale, float(p_drop), seed)
+        ctx.meta = (B, S, H, scale, float(p_drop), seed, bool(causal))
         ctx.save_for_backward(qkv, out, lse, m, dmask)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse, m, dmask = ctx.saved_tensors
-        B, S, H, scale, p_drop, seed = ctx.meta
+        B, S, H, scale, p_drop, seed, causal = ctx.meta
         dout = dout.contiguous()
         delta = torch.empty(B, H, S, dtype=torch.float32, device=qkv.device)
         dqkv = torch.empty_like(qkv)
@@ -60,20 +63,21 @@ class _Attention(torch.autograd.Function):
         # (tiled backward kernels: 64-row workgroups of 4 waves)
         tiled_rows = B * 4 * -(-S // 64)
         cs = torch.empty(tiled_rows, 3 * H * 64, dtype=torch.float32, device=qkv.device)
-        rc = _lib.fn("ddl_attn_bwd")(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), _lib.p(m),
+        name = "ddl_attn_causal_bwd" if causal else "ddl_attn_bwd"
+        rc = _lib.fn(name)(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), _lib.p(m),
                                      delta.data_ptr(), dqkv.data_ptr(), B, S, H, scale, p_drop, _lib.p(dmask),
                                      _lib.p(cs), _lib.stream())
-        if rc not in (0, 2):
-            raise RuntimeError(f"native kernel ddl_attn_bwd failed with HIP error {rc}")
+        if rc not in (0, 2) or (causal and rc != 2):     # causal: always the tiled-row form
+            raise RuntimeError(f"native kernel {name} failed with HIP error {rc}")
         # rides on the gradient: the producing Linear's bias gradient = column sums of these rows
         # (the version guards against autograd accumulating another gradient into dqkv)
         dqkv._ddl_colsum_rows = (cs[:tiled_rows] if rc == 2 else cs[:B], dqkv._version)
-        return dqkv, None, None, None
+        return dqkv, None, None, None, None
 
 
-def attention(qkv, num_heads, mask, dropout_p):
+def attention(qkv, num_heads, mask, dropout_p, causal=False):
     B, S, three_hd = qkv.shape
     if qkv.dtype != torch.bfloat16 or three_hd != 3 * 64 * num_heads:
         from .attention import attention_reference
-        return attention_reference(qkv, num_heads, mask, dropout_p, dropout_p > 0)
-    return _Attention.apply(qkv, num_heads, mask, float(dropout_p))
+        return attention_reference(qkv, num_heads, mask, dropout_p, dropout_p > 0, causal=causal)
+    return _Attention.apply(qkv, num_heads, mask, float(dropout_p), bool(causal))

@@ -154,7 +154,7 @@ class Trainer:
         vocab = min(c.vocab_size, getattr(mc, "vocab_size", c.vocab_size))
         return SyntheticTokens(c.batch_size, c.seq_len, vocab, c.num_classes, self.device,
                                rank=self.rank, seed=c.seed, pool=c.synthetic_pool, pad_fraction=c.pad_fraction,
-                               mlm_predictions=c.mlm_predictions)
+                               mlm_predictions=c.mlm_predictions, causal_lm=c.model.startswith("gpt"))
 
     def _auto_batch(self) -> int:
         from ..utils.memory import fit_batch_size
