@@ -1,0 +1,178 @@
+#!/usr/bin/env python3
+"""GPT-2 generation on one GPU: the KV-cache decode against decoding by full re-forward, and the two
+decode kernels against what the library had before them.
+
+    python benchmarks/gpt2_generate_bench.py [--model gpt2] [--prompt 128] [--new 128] [--batches 1,8,16]
+                                             [--reps 3] [--skip-e2e] [--skip-kernels]
+
+End to end (bf16, random weights, greedy, no eos): ``generate`` (prefill + cached decode steps) and the
+recompute arm (a full ``forward`` over the whole prefix per token, argmax of its last row), timed by a
+host clock around work that ends in a device synchronise; the best of ``--reps`` runs after one warm-up
+run of each arm, the two arms alternating.
+
+Per kernel, timed by device events around ITERS back-to-back calls (so launch overhead is included:
+"call time"), every call on another copy of its large operand (copies totalling >= 512 MB, more than the
+256 MB last-level cache, so the operand comes from HBM):
+  * decode attention at n in {128, 512, 1023} cached keys against ``F.scaled_dot_product_attention`` on
+    the same cache (which neither appends nor needs to: it is handed the n + 1 rows);
+  * the small-M linear on GPT-2 small's five shapes at M in {1, 8, 16} against ``ops.linear``.
+Bytes are what the algorithm must read: 2 (n + 1) 128 B per (batch, head) for attention, N K 2 B for a
+linear; the streaming figure to hold them against is 6.3 TB/s (a float4 copy on this part; 8 TB/s spec).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+STREAM_TBS = 6.3
+ROTATE_BYTES = 512 << 20
+
+
+def _events(fn, iters):
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for i in range(iters):
+        fn(i)
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / iters      # us per call
+
+
+def _best(fn, iters, reps=3):
+    fn(0)
+    _events(fn, max(4, iters // 4))
+    return min(_events(fn, iters) for _ in range(reps))
+
+
+def bench_attention(dev):
+    import torch
+    import torch.nn.functional as F
+    from databricks_distributed_deep_learning_amd import ops
+    H, D, C = 12, 64, 1024
+    for B in (1, 16):
+        per_layer = 2 * B * H * C * D * 2
+        L = min(256, -(-ROTATE_BYTES // per_layer))
+        data = torch.randn(L, 2, B, H, C, D, device=dev).bfloat16()
+        qkv = torch.randn(B, 3 * H * D, device=dev).bfloat16()
+        for n in (128, 512, 1023):
+            lens = torch.full((B,), n, dtype=torch.int32, device=dev)
+            q = qkv.view(B, 3, H, 1, D)[:, 0]
+
+            def ours(i):
+                ops.attention_decode(qkv, data[i % L, 0], data[i % L, 1], lens, H, n + 1)
+
+            def sdpa(i):
+                F.scaled_dot_product_attention(q, data[i % L, 0, :, :, :n + 1], data[i % L, 1, :, :, :n + 1])
+
+            t_o, t_s = _best(ours, 400), _best(sdpa, 400)
+            nbytes = 2 * (n + 1) * D * 2 * B * H
+            print(json.dumps({"kernel": "attention_decode", "B": B, "H": H, "n": n, "copies": L, "us": round(t_o, 2),
+                              "sdpa_us": round(t_s, 2), "GBps": round(nbytes / t_o / 1e3, 1),
+                              "sdpa_GBps": round(nbytes / t_s / 1e3, 1),
+                              "share_of_stream": round(nbytes / t_o / 1e6 / STREAM_TBS, 4)}), flush=True)
+        del data
+
+
+def bench_linear(dev):
+    import torch
+    from databricks_distributed_deep_learning_amd import ops
+    shapes = [("qkv", 2304, 768, None, False), ("attn_out", 768, 768, None, True), ("fc1", 3072, 768, "gelu", False),
+              ("fc2", 768, 3072, None, True), ("head", 50257, 768, None, False)]
+    for name, N, K, act, res in shapes:
+        copies = min(512, -(-ROTATE_BYTES // (N * K * 2)))
+        w = (torch.randn(copies, N, K, device=dev) * K ** -0.5).bfloat16()
+        bias = None if name == "head" else torch.randn(N, device=dev).bfloat16()
+        for M in (1, 8, 16):
+            x = torch.randn(M, K, device=dev).bfloat16()
+            r = torch.randn(M, N, device=dev).bfloat16() if res else None
+
+            def ours(i):
+                ops.linear_small_m(x, w[i % copies], bias, act, r)
+
+            def base(i):
+                ops.linear(x, w[i % copies], bias, act, residual=r)
+
+            with torch.no_grad():
+                t_o, t_b = _best(ours, 300), _best(base, 300)
+            nbytes = N * K * 2
+            print(json.dumps({"kernel": "linear_small_m", "layer": name, "M": M, "N": N, "K": K, "copies": copies,
+                              "us": round(t_o, 2), "ops_linear_us": round(t_b, 2),
+                              "GBps": round(nbytes / t_o / 1e3, 1), "ops_linear_GBps": round(nbytes / t_b / 1e3, 1),
+                              "share_of_stream": round(nbytes / t_o / 1e6 / STREAM_TBS, 4),
+                              "faster_than_ops_linear": bool(t_o < t_b)}), flush=True)
+        del w
+
+
+def bench_e2e(dev, args):
+    import torch
+    from databricks_distributed_deep_learning_amd import models
+    from databricks_distributed_deep_learning_amd.models import cast_params
+    torch.manual_seed(0)
+    model = getattr(models, args.model)(dropout=0.0).to(dev).eval()
+    cast_params(model, torch.bfloat16)
+    for B in [int(b) for b in args.batches.split(",")]:
+        ids = torch.randint(0, model.config.vocab_size, (B, args.prompt), device=dev)
+
+        def cached():
+            return model.generate(ids, max_new_tokens=args.new)
+
+        def recompute():
+            seq = ids
+            with torch.no_grad():
+                for _ in range(args.new):
+                    seq = torch.cat([seq, model(seq)[:, -1].argmax(-1, keepdim=True)], 1)
+            return seq
+
+        def timed(fn):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t, out
+
+        _, a = timed(cached)
+        _, b = timed(recompute)
+        agree = (a == b).float().mean().item()
+        tc, tr = [], []
+        for _ in range(args.reps):
+            tc.append(timed(cached)[0])
+            tr.append(timed(recompute)[0])
+        c, r = min(tc), min(tr)
+        n_tok = B * args.new
+        print(json.dumps({"e2e": args.model, "B": B, "prompt": args.prompt, "new": args.new,
+                          "cached_tokens_per_s": round(n_tok / c, 1), "cached_ms_per_token": round(c / args.new * 1e3, 3),
+                          "recompute_tokens_per_s": round(n_tok / r, 1),
+                          "recompute_ms_per_token": round(r / args.new * 1e3, 3), "speedup": round(r / c, 2),
+                          "cached_s_all": [round(t, 4) for t in tc], "recompute_s_all": [round(t, 4) for t in tr],
+                          "token_agreement": round(agree, 4)}), flush=True)
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="gpt2")
+    ap.add_argument("--prompt", type=int, default=128)
+    ap.add_argument("--new", type=int, default=128)
+    ap.add_argument("--batches", default="1,8,16")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--skip-e2e", action="store_true")
+    ap.add_argument("--skip-kernels", action="store_true")
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("gpt2_generate_bench needs a GPU: times and rates are not measured without one")
+    dev = torch.device("cuda", 0)
+    if not args.skip_e2e:
+        bench_e2e(dev, args)
+    if not args.skip_kernels:
+        bench_attention(dev)
+        bench_linear(dev)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -8,7 +8,7 @@ from .resnet import ResNet, resnet18, resnet34, resnet50, resnet101, resnet152  
 from .bert import BertConfig, BertForSequenceClassification, bert_base, bert_large, bert_tiny  # noqa: F401
 from .bert import BertForPreTraining, bert_base_pretraining, bert_large_pretraining, bert_tiny_pretraining  # noqa: F401
 from .vit import ViTConfig, ViTForImageClassification, vit_b16  # noqa: F401
-from .gpt2 import GPT2Config, GPT2LMHeadModel, gpt2, gpt2_medium, gpt2_large, gpt2_tiny  # noqa: F401
+from .gpt2 import GPT2Config, GPT2LMHeadModel, KVCache, gpt2, gpt2_medium, gpt2_large, gpt2_tiny  # noqa: F401
 from .layers import cast_params, convert_sync_batchnorm  # noqa: F401
 
 _REGISTRY = {

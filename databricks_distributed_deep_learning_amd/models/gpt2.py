@@ -17,6 +17,14 @@ unfused: fc1 without activation, ``F.gelu(approximate="tanh")``, fc2.
 What stays on ATen in a training step: the position-embedding add (``wte(ids) + wpe[:S]``: one
 broadcast add forward, one batch sum + slice backward) and, with ``attention_mask``, the
 ``(1 - mask) * -10000`` key bias; with ``"gelu_new"`` the tanh GELU and its backward.
+
+Generation (``generate``): ``prefill`` runs the causal forward once over the right-padded prompts, copies
+every layer's keys and values into a ``KVCache`` and applies the head to each sequence's last row only;
+``decode_step`` then feeds one token per sequence through ``GPT2Block.decode``: single-query attention
+over the cache (``ops.attention_decode``, which also appends the new key / value) and the M <= 16
+weight-streaming linears (``ops.linear_small_m``).  The cache lengths live on the device, so a step
+launches without a host sync; sampling (temperature, top-k, multinomial) is plain torch on the
+``[B, vocab]`` logits.
 """
 from __future__ import annotations
 
@@ -44,6 +52,34 @@ class GPT2Config:
     attn_pdrop: float = 0.1
     initializer_range: float = 0.02
     activation_function: str = "gelu"       # "gelu" (erf, fused) | "gelu_new" (tanh, unfused)
+
+
+class KVCache:
+    """Keys and values of every layer, ``data [L, 2, B, H, C, D]`` (C: capacity in positions), the valid
+    length of each batch row on the device (``lens``, int32 ``[B]``) and ``max_len``, the host's upper
+    bound on ``lens`` -- what sizes the decode launches, so no step reads ``lens`` back."""
+
+    def __init__(self, data: torch.Tensor, lens: torch.Tensor):
+        self.data, self.lens = data, lens
+        self.capacity = data.shape[4]
+        self.max_len = 0
+
+    @classmethod
+    def allocate(cls, model: "GPT2LMHeadModel", batch: int, capacity: int, device=None, dtype=None) -> "KVCache":
+        c = model.config
+        if not 1 <= capacity <= c.n_positions:
+            raise ValueError(f"capacity {capacity} must be in 1 .. n_positions ({c.n_positions})")
+        w = model.wte.weight
+        device = w.device if device is None else device
+        data = torch.empty(c.n_layer, 2, batch, c.n_head, capacity, c.n_embd // c.n_head,
+                           dtype=w.dtype if dtype is None else dtype, device=device)
+        return cls(data, torch.zeros(batch, dtype=torch.int32, device=device))
+
+    def k(self, layer: int) -> torch.Tensor:
+        return self.data[layer, 0]
+
+    def v(self, layer: int) -> torch.Tensor:
+        return self.data[layer, 1]
 
 
 class GPT2Block(nn.Module):
@@ -85,6 +121,26 @@ class GPT2Block(nn.Module):
         y = self.ln_2(h, grad_from=b2)
         return self._mlp(y, residual=h, residual_grad_to=b2)
 
+    def prefill(self, h, mask, cache: KVCache, layer: int):
+        """The inference forward (no dropout) that also copies this layer's keys / values into the cache."""
+        qkv = self.qkv(self.ln_1(h))
+        ops.kv_cache_fill(qkv, cache.k(layer), cache.v(layer), self.num_heads)
+        h = self.attn_out(ops.attention(qkv, self.num_heads, mask, 0.0, False, causal=True), residual=h)
+        return self._mlp(self.ln_2(h), residual=h)
+
+    def decode(self, h_new, cache: KVCache, layer: int):
+        """One new token per sequence, ``h_new [B, E]``, against the cache (which gains its key / value)."""
+        lin = ops.linear_small_m
+        qkv = lin(self.ln_1(h_new), self.qkv.weight, self.qkv.bias)
+        ctx = ops.attention_decode(qkv, cache.k(layer), cache.v(layer), cache.lens, self.num_heads, cache.max_len + 1)
+        h = lin(ctx, self.attn_out.weight, self.attn_out.bias, residual=h_new)
+        y = self.ln_2(h)
+        if self.tanh_gelu:
+            z = F.gelu(lin(y, self.fc1.weight, self.fc1.bias), approximate="tanh")
+        else:
+            z = lin(y, self.fc1.weight, self.fc1.bias, act="gelu")
+        return lin(z, self.fc2.weight, self.fc2.bias, residual=h)
+
 
 class GPT2LMHeadModel(nn.Module):
     def __init__(self, c: GPT2Config):
@@ -125,6 +181,103 @@ class GPT2LMHeadModel(nn.Module):
                                             -100, defer_weight_ready=True)
             return loss, None
         return ops.linear(h, self.wte.weight, None)
+
+    # ------------------------------------------------------------ generation
+    def prefill(self, input_ids, lens, cache: KVCache):
+        """Right-padded prompts ``[B, S]`` of lengths ``lens`` (int ``[B]``, on the device) -> the next-token
+        logits ``[B, vocab]`` of each sequence's last token; fills ``cache`` and sets its lengths.  The head
+        runs on those B rows only: the ``[B, S, vocab]`` logits never exist."""
+        B, S = input_ids.shape
+        if S > cache.capacity:
+            raise ValueError(f"prompt length {S} exceeds the cache capacity {cache.capacity}")
+        with torch.no_grad():
+            lens = lens.to(device=input_ids.device, dtype=torch.int32)
+            keep = torch.arange(S, device=input_ids.device)[None, :] < lens[:, None]
+            mask_bias = (1.0 - keep.float()) * -10000.0
+            h = self.wte(input_ids) + self.wpe.weight[:S].unsqueeze(0)
+            for i, blk in enumerate(self.h):
+                h = blk.prefill(h, mask_bias, cache, i)
+            last = h[torch.arange(B, device=h.device), (lens - 1).long()]
+            cache.lens.copy_(lens)
+            cache.max_len = S
+            return ops.linear_small_m(self.ln_f(last), self.wte.weight, None)
+
+    def decode_step(self, tokens, cache: KVCache):
+        """``tokens [B]``: the token at position ``cache.lens`` of each sequence -> the next-token logits
+        ``[B, vocab]``.  Every layer appends to the cache; the lengths advance once, after the last."""
+        if cache.max_len + 1 > cache.capacity:
+            raise ValueError(f"max_len {cache.max_len + 1} exceeds the cache capacity {cache.capacity}")
+        with torch.no_grad():
+            h = self.wte(tokens) + self.wpe(cache.lens.long())
+            for i, blk in enumerate(self.h):
+                h = blk.decode(h, cache, i)
+            cache.lens += 1
+            cache.max_len += 1
+            return ops.linear_small_m(self.ln_f(h), self.wte.weight, None)
+
+    @torch.no_grad()
+    def generate(self, input_ids, attention_mask=None, max_new_tokens: int = 20, do_sample: bool = False,
+                 temperature: float = 1.0, top_k=None, eos_token_id=None, pad_token_id=None, generator=None):
+        """Greedy (argmax) or sampled (temperature, then top-k, then multinomial) continuation of
+        ``input_ids [B, S_in]`` -> ``[B, S_in + n_new]``: each row as given, then its generated tokens, with
+        ``pad_token_id`` (default ``eos_token_id``) after the first ``eos_token_id``.  ``attention_mask``
+        rows must each be one contiguous run of ones (left- or right-padded).  Always eval semantics (no
+        dropout).  Stops early once every row has produced ``eos_token_id``: that check is the only host
+        sync of a step and is made only when ``eos_token_id`` is given."""
+        B, S_in = input_ids.shape
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be at least 1")
+        if S_in + max_new_tokens > self.config.n_positions:
+            raise ValueError(f"S_in + max_new_tokens = {S_in + max_new_tokens} exceeds n_positions "
+                             f"{self.config.n_positions}")
+        if do_sample and not temperature > 0:
+            raise ValueError("temperature must be positive")
+        if top_k is not None and top_k < 1:
+            raise ValueError("top_k must be at least 1")
+        dev = input_ids.device
+        ar = torch.arange(S_in, device=dev)[None, :]
+        if attention_mask is None:
+            ids, cnt, S0 = input_ids, torch.full((B,), S_in, dtype=torch.int32, device=dev), S_in
+        else:
+            m = attention_mask.to(dev) != 0
+            cnt = m.sum(1)
+            first = m.int().argmax(1)
+            run = (ar >= first[:, None]) & (ar < (first + cnt)[:, None])
+            if not bool(((run == m).all(1) & (cnt > 0)).all()):
+                raise ValueError("each attention_mask row must be one contiguous, non-empty run of ones")
+            # compact to right-padded: row b's tokens move to columns 0 .. cnt[b]-1
+            ids = input_ids.gather(1, (first[:, None] + ar).clamp(max=S_in - 1))
+            ids = torch.where(ar < cnt[:, None], ids, torch.zeros_like(ids))
+            S0 = int(cnt.max())
+            ids, cnt = ids[:, :S0].contiguous(), cnt.int()
+        if pad_token_id is None:
+            pad_token_id = eos_token_id
+        was_training = self.training
+        self.eval()
+        try:
+            cache = KVCache.allocate(self, B, S0 + max_new_tokens, dev)
+            logits = self.prefill(ids, cnt, cache)
+            done = torch.zeros(B, dtype=torch.bool, device=dev)
+            new = []
+            for i in range(max_new_tokens):
+                if do_sample:
+                    z = logits.float() / temperature
+                    if top_k is not None and top_k < z.shape[-1]:
+                        kth = z.topk(top_k, -1).values[:, -1:]
+                        z = torch.where(z < kth, torch.full_like(z, float("-inf")), z)
+                    tok = torch.multinomial(torch.softmax(z, -1), 1, generator=generator).squeeze(1)
+                else:
+                    tok = logits.argmax(-1)
+                if eos_token_id is not None:
+                    tok = torch.where(done, torch.full_like(tok, pad_token_id), tok)
+                    done = done | (tok == eos_token_id)
+                new.append(tok)
+                if i + 1 == max_new_tokens or (eos_token_id is not None and bool(done.all())):
+                    break
+                logits = self.decode_step(tok, cache)       # finished rows keep decoding (on pad tokens)
+        finally:
+            self.train(was_training)
+        return torch.cat([input_ids, torch.stack(new, 1).to(input_ids.dtype)], 1)
 
 
 def _make(dropout: float, activation_function: str, **kw) -> GPT2LMHeadModel:

@@ -55,3 +55,75 @@ def attention(qkv: torch.Tensor, num_heads: int, mask: Optional[torch.Tensor] = 
         from . import _native_attention
         return _native_attention.attention(qkv, num_heads, mask, dropout_p if training else 0.0, causal)
     return attention_reference(qkv, num_heads, mask, dropout_p, training, causal=causal)
+
+
+# ------------------------------------------------------------------ decode (one new token per sequence, KV cache)
+# cache_k / cache_v: [B, H, C, D], C the capacity in positions; lens: int32 [B], the valid positions of
+# each batch row (on the tensors' device: nothing here reads it on the host).  qkv_new is the new token's
+# packed [B, 3·H·D] projection.  For row b with n = lens[b] the query attends to cached keys 0..n-1 and
+# to the new key, and the new K / V rows are stored to cache[b, :, n].  lens is NOT changed: every layer
+# of a decode step shares it and the caller adds 1 once per step.  max_len is the host's upper bound on
+# n + 1 (it sizes the launch); positions past n never reach the output, whatever they hold.
+def _decode_guard(qkv_new, cache_k, cache_v, lens, max_len):
+    if any(t.requires_grad for t in (qkv_new, cache_k, cache_v)):
+        raise RuntimeError("attention_decode has no autograd: call it under torch.no_grad() on detached tensors")
+    C = cache_k.shape[2]
+    if max_len > C:
+        raise ValueError(f"max_len {max_len} exceeds the cache capacity {C}")
+    if max_len < 1:
+        raise ValueError("max_len counts the new token: at least 1")
+
+
+def attention_decode_reference(qkv_new: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
+                               lens: torch.Tensor, num_heads: int, max_len: int) -> torch.Tensor:
+    _decode_guard(qkv_new, cache_k, cache_v, lens, max_len)
+    B, three_hd = qkv_new.shape
+    D = three_hd // (3 * num_heads)
+    q, k, v = qkv_new.view(B, 3, num_heads, D).unbind(1)
+    n = lens.long()
+    bi = torch.arange(B, device=qkv_new.device)
+    cache_k[bi, :, n] = k.to(cache_k.dtype)
+    cache_v[bi, :, n] = v.to(cache_v.dtype)
+    ct = torch.float64 if qkv_new.dtype == torch.float64 else torch.float32
+    live = torch.arange(max_len, device=qkv_new.device).view(1, 1, max_len) <= n.view(B, 1, 1)      # [B, 1, L]
+    kk, vv = cache_k[:, :, :max_len].to(ct), cache_v[:, :, :max_len].to(ct)
+    s = (q.to(ct).unsqueeze(2) @ kk.transpose(-1, -2)).squeeze(2) / math.sqrt(D)       # [B, H, L]
+    # selects, not multiplies: a dead position may hold any bit pattern
+    p = torch.softmax(torch.where(live, s, torch.full_like(s, float("-inf"))), -1)
+    vv = torch.where(live.unsqueeze(-1), vv, torch.zeros_like(vv))
+    o = (p.unsqueeze(2) @ vv).squeeze(2)                                               # [B, H, D]
+    return o.reshape(B, num_heads * D).to(qkv_new.dtype)
+
+
+def attention_decode(qkv_new: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor, lens: torch.Tensor,
+                     num_heads: int, max_len: int) -> torch.Tensor:
+    """Single-query attention over the cache, with the append; returns ``[B, H·D]``."""
+    _decode_guard(qkv_new, cache_k, cache_v, lens, max_len)
+    if (_lib.use_native(qkv_new, cache_k, cache_v, lens) and qkv_new.dtype == torch.bfloat16
+            and cache_k.dtype == torch.bfloat16 and cache_v.dtype == torch.bfloat16
+            and qkv_new.shape[1] == 3 * 64 * num_heads):
+        from . import _native_attn_decode
+        return _native_attn_decode.attention_decode(qkv_new, cache_k, cache_v, lens, num_heads, max_len)
+    return attention_decode_reference(qkv_new, cache_k, cache_v, lens, num_heads, max_len)
+
+
+def kv_cache_fill_reference(qkv: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor, num_heads: int) -> None:
+    B, S, three_hd = qkv.shape
+    D = three_hd // (3 * num_heads)
+    _, k, v = qkv.view(B, S, 3, num_heads, D).permute(2, 0, 3, 1, 4).unbind(0)
+    cache_k[:, :, :S] = k.to(cache_k.dtype)
+    cache_v[:, :, :S] = v.to(cache_v.dtype)
+
+
+def kv_cache_fill(qkv: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor, num_heads: int) -> None:
+    """After a prefill: the K and V thirds of the packed ``[B, S, 3·H·D]`` projection into cache positions
+    0..S-1 (rows past a sequence's own length too: they are dead by ``lens``)."""
+    if any(t.requires_grad for t in (qkv, cache_k, cache_v)):
+        raise RuntimeError("kv_cache_fill has no autograd: call it under torch.no_grad() on detached tensors")
+    if qkv.shape[1] > cache_k.shape[2]:
+        raise ValueError(f"sequence length {qkv.shape[1]} exceeds the cache capacity {cache_k.shape[2]}")
+    if (_lib.use_native(qkv, cache_k, cache_v) and qkv.dtype == torch.bfloat16 and cache_k.dtype == torch.bfloat16
+            and cache_v.dtype == torch.bfloat16 and qkv.shape[2] == 3 * 64 * num_heads):
+        from . import _native_attn_decode
+        return _native_attn_decode.kv_cache_fill(qkv, cache_k, cache_v, num_heads)
+    return kv_cache_fill_reference(qkv, cache_k, cache_v, num_heads)

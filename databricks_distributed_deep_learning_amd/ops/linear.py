@@ -62,3 +62,22 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
     from .bridge import join
     y = linear_reference(join(x, grad_residual), w, b, act)
     return y if residual is None else y + residual
+
+
+def linear_small_m(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, act: Optional[str] = None,
+                   residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``act(x W^T + b) + residual`` for a decode step's few rows (no autograd): the weight-streaming
+    kernel for M <= 16 rows, bf16 and K % 8 == 0 (any N), ``ops.linear`` for everything else."""
+    if any(t is not None and t.requires_grad for t in (x, w, b, residual)) and torch.is_grad_enabled():
+        raise RuntimeError("linear_small_m has no autograd: call it under torch.no_grad()")
+    K, N = x.shape[-1], w.shape[0]
+    M = x.numel() // K if K else 0
+    if (_lib.use_native(x) and 1 <= M <= 16 and K % 8 == 0 and K >= 8 and act in (None, "gelu")
+            and all(t is None or t.dtype == torch.bfloat16 for t in (x, w, b, residual))
+            and not (residual is not None and act is not None)):
+        from . import _native_linear_decode
+        x2 = x.reshape(M, K).contiguous()
+        r2 = None if residual is None else residual.reshape(M, N).contiguous()
+        y = _native_linear_decode.linear_small_m(x2, w.contiguous(), b, act, r2)
+        return y.view(*x.shape[:-1], N)
+    return linear(x, w, b, act, residual=residual)
