@@ -3,12 +3,17 @@
 decode kernels against what the library had before them.
 
     python benchmarks/gpt2_generate_bench.py [--model gpt2] [--prompt 128] [--new 128] [--batches 1,8,16]
-                                             [--reps 3] [--skip-e2e] [--skip-kernels]
+                                             [--reps 3] [--skip-e2e] [--skip-recompute] [--skip-glue]
+                                             [--skip-kernels]
 
-End to end (bf16, random weights, greedy, no eos): ``generate`` (prefill + cached decode steps) and the
-recompute arm (a full ``forward`` over the whole prefix per token, argmax of its last row), timed by a
+End to end (bf16, random weights, greedy, no eos): ``generate`` (prefill + cached decode steps), the same
+with ``use_graph=True`` (the decode step captured once and replayed; the capture is timed once, apart) and
+the recompute arm (a full ``forward`` over the whole prefix per token, argmax of its last row), timed by a
 host clock around work that ends in a device synchronise; the best of ``--reps`` runs after one warm-up
-run of each arm, the two arms alternating.
+run of each arm, the arms alternating in one process.
+
+The step's glue (``ops.decode_embed``, ``ops.next_token``) at V = 50257 and B in {1, 16} against the ATen
+sequences it replaces, as call times.
 
 Per kernel, timed by device events around ITERS back-to-back calls (so launch overhead is included:
 "call time"), every call on another copy of its large operand (copies totalling >= 512 MB, more than the
@@ -112,6 +117,7 @@ def bench_e2e(dev, args):
     import torch
     from databricks_distributed_deep_learning_amd import models
     from databricks_distributed_deep_learning_amd.models import cast_params
+    from databricks_distributed_deep_learning_amd.models._decode_graph import round_capacity, session_for
     torch.manual_seed(0)
     model = getattr(models, args.model)(dropout=0.0).to(dev).eval()
     cast_params(model, torch.bfloat16)
@@ -128,6 +134,9 @@ def bench_e2e(dev, args):
                     seq = torch.cat([seq, model(seq)[:, -1].argmax(-1, keepdim=True)], 1)
             return seq
 
+        def graphed():
+            return model.generate(ids, max_new_tokens=args.new, use_graph=True)
+
         def timed(fn):
             torch.cuda.synchronize()
             t = time.perf_counter()
@@ -135,21 +144,95 @@ def bench_e2e(dev, args):
             torch.cuda.synchronize()
             return time.perf_counter() - t, out
 
+        # the session (cache, state, warm-up and capture of the step) is built once per shape: timed apart
+        t_capture, sess = timed(lambda: session_for(model, B, round_capacity(args.prompt + args.new,
+                                                                             model.config.n_positions), True))
         _, a = timed(cached)
-        _, b = timed(recompute)
-        agree = (a == b).float().mean().item()
-        tc, tr = [], []
+        _, g = timed(graphed)
+        assert model.decode_session is sess and sess.captures == 1
+        arms = [("cached", cached), ("graph", graphed)]
+        agree = None
+        if not args.skip_recompute:
+            _, b = timed(recompute)
+            agree = (a == b).float().mean().item()
+            arms.append(("recompute", recompute))
+        times = {name: [] for name, _ in arms}
         for _ in range(args.reps):
-            tc.append(timed(cached)[0])
-            tr.append(timed(recompute)[0])
-        c, r = min(tc), min(tr)
+            for name, fn in arms:
+                times[name].append(timed(fn)[0])
+        c, gt = min(times["cached"]), min(times["graph"])
         n_tok = B * args.new
-        print(json.dumps({"e2e": args.model, "B": B, "prompt": args.prompt, "new": args.new,
-                          "cached_tokens_per_s": round(n_tok / c, 1), "cached_ms_per_token": round(c / args.new * 1e3, 3),
-                          "recompute_tokens_per_s": round(n_tok / r, 1),
-                          "recompute_ms_per_token": round(r / args.new * 1e3, 3), "speedup": round(r / c, 2),
-                          "cached_s_all": [round(t, 4) for t in tc], "recompute_s_all": [round(t, 4) for t in tr],
-                          "token_agreement": round(agree, 4)}), flush=True)
+        rec = {"e2e": args.model, "B": B, "prompt": args.prompt, "new": args.new,
+               "cached_tokens_per_s": round(n_tok / c, 1), "cached_ms_per_token": round(c / args.new * 1e3, 3),
+               "graph_tokens_per_s": round(n_tok / gt, 1), "graph_ms_per_token": round(gt / args.new * 1e3, 3),
+               "graph_speedup_over_cached": round(c / gt, 2), "graph_faster": bool(gt < c),
+               "graph_capture_s": round(t_capture, 4), "graph_captures": sess.captures,
+               "graph_token_agreement_with_cached": round((a == g).float().mean().item(), 4),
+               "cached_s_all": [round(t, 4) for t in times["cached"]],
+               "graph_s_all": [round(t, 4) for t in times["graph"]]}
+        if not args.skip_recompute:
+            r = min(times["recompute"])
+            rec.update({"recompute_tokens_per_s": round(n_tok / r, 1),
+                        "recompute_ms_per_token": round(r / args.new * 1e3, 3), "speedup": round(r / c, 2),
+                        "recompute_s_all": [round(t, 4) for t in times["recompute"]],
+                        "token_agreement": round(agree, 4)})
+        print(json.dumps(rec), flush=True)
+
+
+def bench_glue(dev):
+    """``decode_embed`` and ``next_token`` at GPT-2 small's sizes against the ATen sequences they replace
+    (call times: device events around back-to-back calls, launch overhead included)."""
+    import torch
+    from databricks_distributed_deep_learning_amd import ops
+    V, E, P = 50257, 768, 1024
+    wte, wpe = torch.randn(V, E, device=dev).bfloat16(), torch.randn(P, E, device=dev).bfloat16()
+    for B in (1, 16):
+        tok = torch.randint(0, V, (B,), device=dev)
+        lens = torch.randint(0, P - 1, (B,), device=dev).int()
+        logits = (torch.randn(B, V, device=dev) * 2).bfloat16()
+        u = torch.rand(1, B, device=dev)
+        done = torch.zeros(B, dtype=torch.bool, device=dev)
+        step = torch.zeros(B, dtype=torch.int32, device=dev)
+        tokens_out = torch.zeros(B, 1, dtype=torch.int64, device=dev)
+        out = torch.zeros(B, dtype=torch.int64, device=dev)
+        lens2 = lens.clone()
+        greedy = ops.next_token_params(eos_token_id=0, sample=False, device=dev)
+        sampled = ops.next_token_params(1.0 / 0.8, 50, eos_token_id=0, device=dev)
+
+        def embed(i):
+            ops.decode_embed(tok, lens, wte, wpe)
+
+        def embed_aten(i):
+            ops.embedding(tok, wte) + ops.embedding(lens.long(), wpe)
+
+        def pick(params):
+            def f(i):
+                ops.next_token(logits, u=u, params=params, step=step, done=done, out=out, tokens_out=tokens_out,
+                               lens=lens2)
+            return f
+
+        def greedy_aten(i):
+            t = logits.argmax(-1)
+            t = torch.where(done, torch.full_like(t, 0), t)
+            d = done | (t == 0)     # noqa: F841
+            lens2.add_(1)
+
+        def sampled_aten(i):
+            z = logits.float() / 0.8
+            kth = z.topk(50, -1).values[:, -1:]
+            z = torch.where(z < kth, torch.full_like(z, float("-inf")), z)
+            t = torch.multinomial(torch.softmax(z, -1), 1).squeeze(1)
+            t = torch.where(done, torch.full_like(t, 0), t)
+            d = done | (t == 0)     # noqa: F841
+            lens2.add_(1)
+
+        with torch.no_grad():
+            rows = [("decode_embed", _best(embed, 400), _best(embed_aten, 400)),
+                    ("next_token greedy", _best(pick(greedy), 400), _best(greedy_aten, 400)),
+                    ("next_token top-50 T=0.8", _best(pick(sampled), 400), _best(sampled_aten, 400))]
+        for name, t_o, t_a in rows:
+            print(json.dumps({"kernel": name, "B": B, "V": V, "E": E, "us": round(t_o, 2), "aten_us": round(t_a, 2),
+                              "faster_than_aten": bool(t_o < t_a)}), flush=True)
 
 
 def main() -> int:
@@ -161,6 +244,8 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--skip-e2e", action="store_true")
     ap.add_argument("--skip-kernels", action="store_true")
+    ap.add_argument("--skip-recompute", action="store_true", help="end to end: the cached and graph arms only")
+    ap.add_argument("--skip-glue", action="store_true")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -168,6 +253,8 @@ def main() -> int:
     dev = torch.device("cuda", 0)
     if not args.skip_e2e:
         bench_e2e(dev, args)
+    if not args.skip_glue:
+        bench_glue(dev)
     if not args.skip_kernels:
         bench_attention(dev)
         bench_linear(dev)

@@ -1,0 +1,115 @@
+"""A GPT-2 decode session: the static state of a generation loop and its step, captured once.
+
+The step is one linear chain on one stream -- ``ops.decode_embed``, every block's ``decode`` with the
+attention launch bound fixed at the cache capacity (so the grid is the same at every step; rows past
+``lens`` are still never loaded), ``ln_f``, the head ``ops.linear_small_m`` and ``ops.next_token``, which
+also advances the cache lengths and the step counter -- and it reads and writes only the session's own
+tensors, so on the GPU it is captured into a ``torch.cuda.CUDAGraph`` and replayed: one host call per token
+instead of about a hundred.  Off the GPU (or without the native kernels) the same step runs eagerly.
+"""
+from __future__ import annotations
+
+import weakref
+
+import torch
+
+from .. import ops
+
+_sessions: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()     # model -> its DecodeSession
+
+
+def round_capacity(need: int, n_positions: int) -> int:
+    """``need`` positions rounded up to a multiple of 128, capped at ``n_positions``."""
+    return min((need + 127) // 128 * 128, n_positions)
+
+
+def _key(model, batch: int, capacity: int, graph: bool):
+    w = model.wte.weight
+    return (batch, capacity, w.device, w.dtype, graph, tuple(p.data_ptr() for p in model.parameters()))
+
+
+def session_for(model, batch: int, capacity: int, graph: bool) -> "DecodeSession":
+    """The model's session for this shape: rebuilt when the batch, the capacity, the device, the dtype or
+    the address of any parameter baked into the captured step has changed."""
+    key = _key(model, batch, capacity, graph)
+    s = _sessions.get(model)
+    if s is None or s.key != key:
+        s = None
+        _sessions.pop(model, None)          # (frees the old session's cache before the new one is allocated)
+        s = _sessions[model] = DecodeSession(model, batch, capacity, graph, key)
+    return s
+
+
+def current_session(model):
+    return _sessions.get(model)
+
+
+class DecodeSession:
+    WARMUP = 2
+
+    def __init__(self, model, batch: int, capacity: int, graph: bool, key=None):
+        from .gpt2 import KVCache
+        dev = model.wte.weight.device
+        self.key = key
+        self._model = weakref.ref(model)
+        self.batch, self.capacity = batch, capacity
+        self.cache = KVCache.allocate(model, batch, capacity, dev)
+        self.tok_cur = torch.zeros(batch, dtype=torch.int64, device=dev)
+        self.done = torch.zeros(batch, dtype=torch.bool, device=dev)
+        self.step = torch.zeros(batch, dtype=torch.int32, device=dev)
+        self.u = torch.zeros(capacity, batch, dtype=torch.float32, device=dev)
+        self.tokens_out = torch.zeros(batch, capacity, dtype=torch.int64, device=dev)
+        self.params = ops.next_token_params(device=dev)
+        self.captures = 0
+        self.graph = None
+        if graph:
+            self._capture()
+
+    def _state(self):
+        return (self.cache.lens, self.tok_cur, self.done, self.step, self.tokens_out)
+
+    def _step(self):
+        m, c = self._model(), self.cache
+        h = ops.decode_embed(self.tok_cur, c.lens, m.wte.weight, m.wpe.weight)
+        for i, blk in enumerate(m.h):
+            h = blk.decode(h, c, i, len_bound=c.capacity)
+        logits = ops.linear_small_m(m.ln_f(h), m.wte.weight, None)
+        ops.next_token(logits, u=self.u, params=self.params, step=self.step, done=self.done, out=self.tok_cur,
+                       tokens_out=self.tokens_out, lens=c.lens)
+
+    def _capture(self):
+        # the warm-up really executes (on a side stream, as export.GraphRunner's): it writes dead cache rows,
+        # which get rewritten, and advances the state, which is put back -- or lens would walk off the cache
+        saved = [t.clone() for t in self._state()]
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s), torch.no_grad():
+            for _ in range(min(self.WARMUP, self.capacity)):
+                self._step()
+        torch.cuda.current_stream().wait_stream(s)
+        for t, v in zip(self._state(), saved):
+            t.copy_(v)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self.graph):
+            self._step()
+        self.captures += 1
+
+    def begin(self, params: torch.Tensor, u=None):
+        """Before a generation: fresh counters and flags, this call's settings and uniform numbers."""
+        self.done.zero_()
+        self.step.zero_()
+        self.params.copy_(params)
+        if u is not None:
+            self.u[:u.shape[0]].copy_(u)
+
+    def first_token(self, logits: torch.Tensor):
+        """From the prefill's logits, by the step's own kernel; prefill has already set the lengths."""
+        ops.next_token(logits, u=self.u, params=self.params, step=self.step, done=self.done, out=self.tok_cur,
+                       tokens_out=self.tokens_out)
+
+    def advance(self):
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            with torch.no_grad():
+                self._step()

@@ -24,7 +24,10 @@ every layer's keys and values into a ``KVCache`` and applies the head to each se
 over the cache (``ops.attention_decode``, which also appends the new key / value) and the M <= 16
 weight-streaming linears (``ops.linear_small_m``).  The cache lengths live on the device, so a step
 launches without a host sync; sampling (temperature, top-k, multinomial) is plain torch on the
-``[B, vocab]`` logits.
+``[B, vocab]`` logits.  ``generate(use_graph=True)`` runs the step from a decode session instead
+(``models/_decode_graph.py``): ``ops.decode_embed`` and ``ops.next_token`` replace the ATen glue and the
+sampling, the attention launch bound is the cache capacity at every step, and the step is captured once into
+a hipGraph and replayed per token.
 """
 from __future__ import annotations
 
@@ -128,11 +131,13 @@ class GPT2Block(nn.Module):
         h = self.attn_out(ops.attention(qkv, self.num_heads, mask, 0.0, False, causal=True), residual=h)
         return self._mlp(self.ln_2(h), residual=h)
 
-    def decode(self, h_new, cache: KVCache, layer: int):
-        """One new token per sequence, ``h_new [B, E]``, against the cache (which gains its key / value)."""
+    def decode(self, h_new, cache: KVCache, layer: int, len_bound=None):
+        """One new token per sequence, ``h_new [B, E]``, against the cache (which gains its key / value).
+        ``len_bound``: the bound on ``lens + 1`` that sizes the attention launch (default ``max_len + 1``)."""
         lin = ops.linear_small_m
         qkv = lin(self.ln_1(h_new), self.qkv.weight, self.qkv.bias)
-        ctx = ops.attention_decode(qkv, cache.k(layer), cache.v(layer), cache.lens, self.num_heads, cache.max_len + 1)
+        ctx = ops.attention_decode(qkv, cache.k(layer), cache.v(layer), cache.lens, self.num_heads,
+                                   cache.max_len + 1 if len_bound is None else len_bound)
         h = lin(ctx, self.attn_out.weight, self.attn_out.bias, residual=h_new)
         y = self.ln_2(h)
         if self.tanh_gelu:
@@ -202,28 +207,46 @@ class GPT2LMHeadModel(nn.Module):
             cache.max_len = S
             return ops.linear_small_m(self.ln_f(last), self.wte.weight, None)
 
-    def decode_step(self, tokens, cache: KVCache):
+    def decode_step(self, tokens, cache: KVCache, len_bound=None):
         """``tokens [B]``: the token at position ``cache.lens`` of each sequence -> the next-token logits
-        ``[B, vocab]``.  Every layer appends to the cache; the lengths advance once, after the last."""
+        ``[B, vocab]``.  Every layer appends to the cache; the lengths advance once, after the last.
+        ``len_bound`` (default ``cache.max_len + 1``): the bound on ``lens + 1`` handed to the attention
+        launches; with ``cache.capacity`` every step launches the same grid (positions past ``lens`` are
+        still never loaded)."""
         if cache.max_len + 1 > cache.capacity:
             raise ValueError(f"max_len {cache.max_len + 1} exceeds the cache capacity {cache.capacity}")
+        if len_bound is not None and not cache.max_len + 1 <= len_bound <= cache.capacity:
+            raise ValueError(f"len_bound {len_bound} must be in max_len + 1 ({cache.max_len + 1}) .. the cache "
+                             f"capacity ({cache.capacity})")
         with torch.no_grad():
             h = self.wte(tokens) + self.wpe(cache.lens.long())
             for i, blk in enumerate(self.h):
-                h = blk.decode(h, cache, i)
+                h = blk.decode(h, cache, i, len_bound)
             cache.lens += 1
             cache.max_len += 1
             return ops.linear_small_m(self.ln_f(h), self.wte.weight, None)
 
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, max_new_tokens: int = 20, do_sample: bool = False,
-                 temperature: float = 1.0, top_k=None, eos_token_id=None, pad_token_id=None, generator=None):
+                 temperature: float = 1.0, top_k=None, eos_token_id=None, pad_token_id=None, generator=None,
+                 use_graph: bool = False):
         """Greedy (argmax) or sampled (temperature, then top-k, then multinomial) continuation of
         ``input_ids [B, S_in]`` -> ``[B, S_in + n_new]``: each row as given, then its generated tokens, with
         ``pad_token_id`` (default ``eos_token_id``) after the first ``eos_token_id``.  ``attention_mask``
         rows must each be one contiguous run of ones (left- or right-padded).  Always eval semantics (no
         dropout).  Stops early once every row has produced ``eos_token_id``: that check is the only host
-        sync of a step and is made only when ``eos_token_id`` is given."""
+        sync of a step and is made only when ``eos_token_id`` is given.
+
+        ``use_graph=True``: the decode step runs from a session cached on the model
+        (``models/_decode_graph.py``): its state lives on the device, tokens are chosen by
+        ``ops.next_token``, and on a GPU with the native kernels and bf16 parameters the whole step is one
+        captured graph, replayed once per token (captured on the first call of a shape; rebuilt when the
+        batch, the rounded cache capacity or a parameter's storage changes).  Elsewhere the same loop runs
+        eagerly through the reference ops.  Greedy output equals ``use_graph=False``'s.  With ``do_sample``
+        the tokens follow ``ops.next_token``'s definition from one ``torch.rand(max_new_tokens, B,
+        generator=generator)`` drawn before the loop: the same distribution as the ``torch.multinomial``
+        path, but NOT its token stream for a given generator.  The eos check syncs only every 16 steps; the
+        result is trimmed to the length ``use_graph=False`` returns."""
         B, S_in = input_ids.shape
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be at least 1")
@@ -254,6 +277,13 @@ class GPT2LMHeadModel(nn.Module):
             pad_token_id = eos_token_id
         was_training = self.training
         self.eval()
+        if use_graph:
+            try:
+                new = self._generate_session(ids, cnt, S0 + max_new_tokens, max_new_tokens, do_sample, temperature,
+                                             top_k, eos_token_id, pad_token_id, generator)
+            finally:
+                self.train(was_training)
+            return torch.cat([input_ids, new.to(input_ids.dtype)], 1)
         try:
             cache = KVCache.allocate(self, B, S0 + max_new_tokens, dev)
             logits = self.prefill(ids, cnt, cache)
@@ -278,6 +308,41 @@ class GPT2LMHeadModel(nn.Module):
         finally:
             self.train(was_training)
         return torch.cat([input_ids, torch.stack(new, 1).to(input_ids.dtype)], 1)
+
+    @property
+    def decode_session(self):
+        """The session ``generate(use_graph=True)`` last used on this model (None before the first)."""
+        from ._decode_graph import current_session
+        return current_session(self)
+
+    def _generate_session(self, ids, cnt, need, max_new_tokens, do_sample, temperature, top_k, eos_token_id,
+                          pad_token_id, generator):
+        """``generate``'s loop on a decode session -> the new tokens ``[B, n_new]``."""
+        from ..ops import _lib
+        from ._decode_graph import round_capacity, session_for
+        B, dev, w = ids.shape[0], ids.device, self.wte.weight
+        graph = dev.type == "cuda" and w.dtype == torch.bfloat16 and _lib.use_native(w)
+        sess = session_for(self, B, round_capacity(need, self.config.n_positions), graph)
+        u = None
+        if do_sample:
+            u = torch.rand(max_new_tokens, B, generator=generator,
+                           device=dev if generator is None else generator.device).to(dev)
+        sess.begin(ops.next_token_params(1.0 / temperature if do_sample else 1.0, top_k, eos_token_id, pad_token_id,
+                                         do_sample, dev), u)
+        sess.first_token(self.prefill(ids, cnt, sess.cache))
+        n = 1
+        while n < max_new_tokens:
+            sess.advance()
+            n += 1
+            if eos_token_id is not None and n % 16 == 0 and bool(sess.done.all()):
+                break
+        new = sess.tokens_out[:, :n].clone()
+        if eos_token_id is not None:
+            # what the per-step check returns: through the step in which the last row emitted eos
+            is_eos = new == eos_token_id
+            if bool(is_eos.any(1).all()):
+                new = new[:, :int(is_eos.int().argmax(1).max()) + 1]
+        return new
 
 
 def _make(dropout: float, activation_function: str, **kw) -> GPT2LMHeadModel:
