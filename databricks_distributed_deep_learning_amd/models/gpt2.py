@@ -28,6 +28,11 @@ launches without a host sync; sampling (temperature, top-k, multinomial) is plai
 (``models/_decode_graph.py``): ``ops.decode_embed`` and ``ops.next_token`` replace the ATen glue and the
 sampling, the attention launch bound is the cache capacity at every step, and the step is captured once into
 a hipGraph and replayed per token.
+
+``extend`` appends a chunk of T tokens per sequence to a cache that already holds something
+(``ops.attention_extend``: the chunk's queries over the cached keys plus, causally, the chunk's own; it appends
+too).  ``generate(prefix=cache)`` starts from a copy of a prefilled cache (``KVCache.copy_prefix_``: a shared
+system prompt is computed once) and ``generate(prefill_chunk=k)`` consumes the prompt k columns at a time.
 """
 from __future__ import annotations
 
@@ -84,6 +89,29 @@ class KVCache:
     def v(self, layer: int) -> torch.Tensor:
         return self.data[layer, 1]
 
+    def copy_prefix_(self, src: "KVCache") -> "KVCache":
+        """Start this cache from ``src``'s contents: positions ``< src.max_len`` of every layer, ``lens`` and
+        ``max_len``.  ``src`` has this cache's batch or batch 1 (one prefix shared by every row), its dtype and
+        its device (nothing is converted or moved silently); it is only read.  Rows of ``src`` may have unequal
+        ``lens``: ``src.max_len``, their bound, is what is copied and what ``generate`` counts against
+        ``n_positions``."""
+        L, _, B, H, C, D = self.data.shape
+        Ls, _, Bs, Hs, _, Ds = src.data.shape
+        if (Ls, Hs, Ds) != (L, H, D):
+            raise ValueError(f"prefix cache has {Ls} layers of {Hs} heads x {Ds}, this one {L} of {H} x {D}")
+        if Bs not in (1, B):
+            raise ValueError(f"prefix cache batch {Bs} must be 1 or {B}")
+        if src.data.dtype != self.data.dtype or src.data.device != self.data.device:
+            raise ValueError(f"prefix cache is {src.data.dtype} on {src.data.device}, this one {self.data.dtype} on "
+                             f"{self.data.device}")
+        if src.max_len > C:
+            raise ValueError(f"prefix length {src.max_len} exceeds the cache capacity {C}")
+        n = src.max_len
+        self.data[:, :, :, :, :n].copy_(src.data[:, :, :, :, :n])
+        self.lens.copy_(src.lens)
+        self.max_len = n
+        return self
+
 
 class GPT2Block(nn.Module):
     def __init__(self, c: GPT2Config):
@@ -138,13 +166,33 @@ class GPT2Block(nn.Module):
         qkv = lin(self.ln_1(h_new), self.qkv.weight, self.qkv.bias)
         ctx = ops.attention_decode(qkv, cache.k(layer), cache.v(layer), cache.lens, self.num_heads,
                                    cache.max_len + 1 if len_bound is None else len_bound)
-        h = lin(ctx, self.attn_out.weight, self.attn_out.bias, residual=h_new)
+        return self._small_m_tail(ctx, h_new)
+
+    def _small_m_tail(self, ctx, h):
+        """Output projection and MLP of a block on M <= 16 rows (``ops.linear_small_m``)."""
+        lin = ops.linear_small_m
+        h = lin(ctx, self.attn_out.weight, self.attn_out.bias, residual=h)
         y = self.ln_2(h)
         if self.tanh_gelu:
             z = F.gelu(lin(y, self.fc1.weight, self.fc1.bias), approximate="tanh")
         else:
             z = lin(y, self.fc1.weight, self.fc1.bias, act="gelu")
         return lin(z, self.fc2.weight, self.fc2.bias, residual=h)
+
+    def extend(self, h, cache: KVCache, layer: int, new_lens=None, len_bound=None):
+        """A chunk of new tokens per sequence, ``h [B, T, E]``, against the cache, which gains the keys /
+        values of each row's first ``new_lens`` (default T) tokens: ``prefill`` with ``ops.attention_extend``
+        in place of attention + fill.  ``len_bound``: the bound on ``lens`` (default ``max_len``).  With
+        ``B T <= 16`` the linears are the weight-streaming ones of ``decode``."""
+        small = h.shape[0] * h.shape[1] <= 16
+        y = self.ln_1(h)
+        qkv = ops.linear_small_m(y, self.qkv.weight, self.qkv.bias) if small else self.qkv(y)
+        ctx = ops.attention_extend(qkv, cache.k(layer), cache.v(layer), cache.lens, self.num_heads,
+                                   cache.max_len if len_bound is None else len_bound, new_lens)
+        if small:
+            return self._small_m_tail(ctx, h)
+        h = self.attn_out(ctx, residual=h)
+        return self._mlp(self.ln_2(h), residual=h)
 
 
 class GPT2LMHeadModel(nn.Module):
@@ -207,6 +255,64 @@ class GPT2LMHeadModel(nn.Module):
             cache.max_len = S
             return ops.linear_small_m(self.ln_f(last), self.wte.weight, None)
 
+    def extend(self, input_ids, cache: KVCache, new_lens=None, all_logits: bool = False):
+        """``input_ids [B, T]``: the tokens at positions ``cache.lens + 0 .. T-1`` of each sequence, right-padded
+        to T, of which row b's first ``new_lens[b]`` are real (int ``[B]`` on the device; default T) -> the
+        next-token logits ``[B, vocab]`` at each row's last new token (the head runs on those B rows only), or
+        with ``all_logits`` the ``[B, T, vocab]`` logits of every column (padded ones are meaningless).  Every
+        layer appends the real tokens' keys / values; then ``cache.lens += new_lens`` and ``cache.max_len +=
+        T``.  From an empty cache this is ``prefill``.
+
+        ``new_lens[b] == 0`` is allowed: the row is handed one dead column (the attention wants at least one
+        query per row), whose key / value land at position ``lens[b]`` -- which stays dead, since the row's
+        length does not advance, and is overwritten by the row's next real token.  Its logits are meaningless."""
+        B, T = input_ids.shape
+        if T < 1:
+            raise ValueError("extend needs at least one column")
+        if cache.max_len + T > cache.capacity:
+            raise ValueError(f"max_len {cache.max_len} + {T} new columns exceeds the cache capacity {cache.capacity}")
+        with torch.no_grad():
+            dev = input_ids.device
+            adv = q_lens = None
+            if new_lens is not None:
+                adv = new_lens.to(device=dev, dtype=torch.int32).clamp(0, T)
+                q_lens = adv.clamp(min=1)
+            # positions lens + i, read on the device; a padded column's may pass the table: clamped
+            pos = cache.lens.long()[:, None] + torch.arange(T, device=dev)[None, :]
+            h = self.wte(input_ids) + self.wpe(pos.clamp(max=self.config.n_positions - 1))
+            for i, blk in enumerate(self.h):
+                h = blk.extend(h, cache, i, q_lens)
+            if all_logits:
+                logits = ops.linear(self.ln_f(h), self.wte.weight, None)
+            else:
+                last = h[:, -1] if q_lens is None else h[torch.arange(B, device=dev), (q_lens - 1).long()]
+                logits = ops.linear_small_m(self.ln_f(last), self.wte.weight, None)
+            cache.lens += T if adv is None else adv
+            cache.max_len += T
+            return logits
+
+    def _consume_prompt(self, ids, cnt, cache: KVCache, prefix=None, prefill_chunk=None):
+        """The right-padded prompts ``ids [B, S0]`` of lengths ``cnt`` into ``cache`` -> each row's next-token
+        logits.  Neither option: ``prefill``.  Otherwise the cache starts from ``prefix`` (or empty) and takes
+        the prompt through ``extend`` in chunks of ``prefill_chunk`` columns (default: all at once).  A row
+        whose prompt ended before a chunk passes ``new_lens = 0`` there (see ``extend``) and keeps the logits
+        of the chunk that held its last token."""
+        if prefix is None and prefill_chunk is None:
+            return self.prefill(ids, cnt, cache)
+        if prefix is not None:
+            cache.copy_prefix_(prefix)
+        else:
+            cache.lens.zero_()
+            cache.max_len = 0
+        S0 = ids.shape[1]
+        step = S0 if prefill_chunk is None else prefill_chunk
+        logits = None
+        for c0 in range(0, S0, step):
+            T = min(step, S0 - c0)
+            new = self.extend(ids[:, c0:c0 + T], cache, (cnt - c0).clamp(0, T))
+            logits = new if logits is None else torch.where((cnt > c0)[:, None], new, logits)
+        return logits
+
     def decode_step(self, tokens, cache: KVCache, len_bound=None):
         """``tokens [B]``: the token at position ``cache.lens`` of each sequence -> the next-token logits
         ``[B, vocab]``.  Every layer appends to the cache; the lengths advance once, after the last.
@@ -229,7 +335,7 @@ class GPT2LMHeadModel(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, max_new_tokens: int = 20, do_sample: bool = False,
                  temperature: float = 1.0, top_k=None, eos_token_id=None, pad_token_id=None, generator=None,
-                 use_graph: bool = False):
+                 use_graph: bool = False, prefix: KVCache = None, prefill_chunk: int = None):
         """Greedy (argmax) or sampled (temperature, then top-k, then multinomial) continuation of
         ``input_ids [B, S_in]`` -> ``[B, S_in + n_new]``: each row as given, then its generated tokens, with
         ``pad_token_id`` (default ``eos_token_id``) after the first ``eos_token_id``.  ``attention_mask``
@@ -246,13 +352,22 @@ class GPT2LMHeadModel(nn.Module):
         the tokens follow ``ops.next_token``'s definition from one ``torch.rand(max_new_tokens, B,
         generator=generator)`` drawn before the loop: the same distribution as the ``torch.multinomial``
         path, but NOT its token stream for a given generator.  The eos check syncs only every 16 steps; the
-        result is trimmed to the length ``use_graph=False`` returns."""
+        result is trimmed to the length ``use_graph=False`` returns.
+
+        ``prefix``: a ``KVCache`` (of batch B, or of batch 1 and shared by every row) that already holds the
+        tokens before ``input_ids``, e.g. a system prompt prefilled once: it is copied into this call's own
+        cache, never modified, and the prompt is consumed by ``extend`` on top of it.  ``prefill_chunk``: the
+        prompt is consumed in chunks of that many columns through ``extend`` (the first one included), which
+        bounds the prompt's activations by the chunk.  Without either, the prompt goes through ``prefill``."""
         B, S_in = input_ids.shape
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be at least 1")
-        if S_in + max_new_tokens > self.config.n_positions:
-            raise ValueError(f"S_in + max_new_tokens = {S_in + max_new_tokens} exceeds n_positions "
-                             f"{self.config.n_positions}")
+        if prefill_chunk is not None and prefill_chunk < 1:
+            raise ValueError("prefill_chunk must be at least 1")
+        P0 = 0 if prefix is None else prefix.max_len
+        if P0 + S_in + max_new_tokens > self.config.n_positions:
+            raise ValueError(f"{'prefix + ' if prefix is not None else ''}S_in + max_new_tokens = "
+                             f"{P0 + S_in + max_new_tokens} exceeds n_positions {self.config.n_positions}")
         if do_sample and not temperature > 0:
             raise ValueError("temperature must be positive")
         if top_k is not None and top_k < 1:
@@ -279,14 +394,15 @@ class GPT2LMHeadModel(nn.Module):
         self.eval()
         if use_graph:
             try:
-                new = self._generate_session(ids, cnt, S0 + max_new_tokens, max_new_tokens, do_sample, temperature,
-                                             top_k, eos_token_id, pad_token_id, generator)
+                new = self._generate_session(ids, cnt, P0 + S0 + max_new_tokens, max_new_tokens, do_sample,
+                                             temperature, top_k, eos_token_id, pad_token_id, generator, prefix,
+                                             prefill_chunk)
             finally:
                 self.train(was_training)
             return torch.cat([input_ids, new.to(input_ids.dtype)], 1)
         try:
-            cache = KVCache.allocate(self, B, S0 + max_new_tokens, dev)
-            logits = self.prefill(ids, cnt, cache)
+            cache = KVCache.allocate(self, B, P0 + S0 + max_new_tokens, dev)
+            logits = self._consume_prompt(ids, cnt, cache, prefix, prefill_chunk)
             done = torch.zeros(B, dtype=torch.bool, device=dev)
             new = []
             for i in range(max_new_tokens):
@@ -316,7 +432,7 @@ class GPT2LMHeadModel(nn.Module):
         return current_session(self)
 
     def _generate_session(self, ids, cnt, need, max_new_tokens, do_sample, temperature, top_k, eos_token_id,
-                          pad_token_id, generator):
+                          pad_token_id, generator, prefix=None, prefill_chunk=None):
         """``generate``'s loop on a decode session -> the new tokens ``[B, n_new]``."""
         from ..ops import _lib
         from ._decode_graph import round_capacity, session_for
@@ -329,7 +445,7 @@ class GPT2LMHeadModel(nn.Module):
                            device=dev if generator is None else generator.device).to(dev)
         sess.begin(ops.next_token_params(1.0 / temperature if do_sample else 1.0, top_k, eos_token_id, pad_token_id,
                                          do_sample, dev), u)
-        sess.first_token(self.prefill(ids, cnt, sess.cache))
+        sess.first_token(self._consume_prompt(ids, cnt, sess.cache, prefix, prefill_chunk))
         n = 1
         while n < max_new_tokens:
             sess.advance()

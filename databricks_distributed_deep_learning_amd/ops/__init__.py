@@ -15,7 +15,7 @@ from .conv import conv2d, conv2d_bias_act, patch_embed  # noqa: F401
 from .norm import batch_norm, batch_norm_add_bn, bn_relu_maxpool, layer_norm  # noqa: F401
 from .linear import linear, linear_small_m  # noqa: F401
 from .activation import gelu, dropout, relu  # noqa: F401
-from .attention import attention, attention_decode, kv_cache_fill  # noqa: F401
+from .attention import attention, attention_decode, attention_extend, kv_cache_fill  # noqa: F401
 from .decode import decode_embed, next_token, next_token_params  # noqa: F401
 from .loss import cross_entropy, softmax_topk  # noqa: F401
 from .pool import max_pool2d, global_avg_pool  # noqa: F401

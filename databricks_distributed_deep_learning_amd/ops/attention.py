@@ -127,3 +127,69 @@ def kv_cache_fill(qkv: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tenso
         from . import _native_attn_decode
         return _native_attn_decode.kv_cache_fill(qkv, cache_k, cache_v, num_heads)
     return kv_cache_fill_reference(qkv, cache_k, cache_v, num_heads)
+
+
+# ------------------------------------------------------------------ extend (a chunk of T new tokens per sequence)
+# qkv_new is the chunk's packed [B, T, 3·H·D] projection.  For row b with n = lens[b] and t = new_lens[b]
+# (T without new_lens; 1 <= t <= T: rows are right-padded), query i < t attends to cached keys 0..n-1 and
+# to chunk keys 0..i -- read from qkv_new, never from the cache -- and output rows i >= t are zeros.  The
+# K / V rows of chunk positions i < t are stored to cache[b, :, n+i]; nothing else in the cache changes.
+# (A caller that must pass a row with no real token -- GPT2LMHeadModel.extend with new_lens[b] == 0 -- hands
+# it t = 1: that row's dead position n then does change; it stays dead as long as the caller does not
+# advance lens for it.)
+# lens is NOT changed (every layer shares it; the caller adds new_lens once).  max_len is the host's
+# upper bound on lens; max_len + T must fit the capacity.
+def _extend_guard(qkv_new, cache_k, cache_v, max_len):
+    if any(t.requires_grad for t in (qkv_new, cache_k, cache_v)):
+        raise RuntimeError("attention_extend has no autograd: call it under torch.no_grad() on detached tensors")
+    if qkv_new.dim() != 3 or qkv_new.shape[1] < 1:
+        raise ValueError(f"qkv_new must be [B, T >= 1, 3·H·D], got {tuple(qkv_new.shape)}")
+    C, T = cache_k.shape[2], qkv_new.shape[1]
+    if max_len < 0:
+        raise ValueError("max_len bounds lens: at least 0")
+    if max_len + T > C:
+        raise ValueError(f"max_len {max_len} + the chunk's {T} tokens exceeds the cache capacity {C}")
+
+
+def attention_extend_reference(qkv_new: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
+                               lens: torch.Tensor, num_heads: int, max_len: int,
+                               new_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _extend_guard(qkv_new, cache_k, cache_v, max_len)
+    B, T, three_hd = qkv_new.shape
+    D = three_hd // (3 * num_heads)
+    dev = qkv_new.device
+    q, k, v = qkv_new.view(B, T, 3, num_heads, D).permute(2, 0, 3, 1, 4).unbind(0)     # [B, H, T, D]
+    n = lens.long().clamp(0, max_len)
+    t = torch.full_like(n, T) if new_lens is None else new_lens.long().clamp(1, T)
+    ct = torch.float64 if qkv_new.dtype == torch.float64 else torch.float32
+    i = torch.arange(T, device=dev)
+    qlive = i.view(1, T) < t.view(B, 1)                                                # [B, T]
+    # keys: the cache's first max_len positions (live while < n), then the chunk (live while <= the query)
+    live = torch.cat([(torch.arange(max_len, device=dev).view(1, 1, max_len) < n.view(B, 1, 1)).expand(B, T, max_len),
+                      (i.view(1, 1, T) <= i.view(1, T, 1)).expand(B, T, T)], 2).unsqueeze(1)    # [B, 1, T, L + T]
+    kk = torch.cat([cache_k[:, :, :max_len].to(ct), k.to(ct)], 2)
+    vv = torch.cat([cache_v[:, :, :max_len].to(ct), v.to(ct)], 2)
+    s = q.to(ct) @ kk.transpose(-1, -2) / math.sqrt(D)                                 # [B, H, T, L + T]
+    # selects, not multiplies: a dead position (and a padded chunk row) may hold any bit pattern
+    p = torch.softmax(torch.where(live, s, torch.full_like(s, float("-inf"))), -1)
+    vlive = torch.cat([torch.arange(max_len, device=dev).view(1, max_len) < n.view(B, 1), qlive], 1)   # [B, L + T]
+    vv = torch.where(vlive.view(B, 1, -1, 1), vv, torch.zeros_like(vv))
+    o = torch.where(qlive.view(B, 1, T, 1), p @ vv, torch.zeros((), dtype=ct, device=dev))
+    # the append: chunk position i < t of row b to cache position n + i
+    bi, ii = torch.nonzero(qlive, as_tuple=True)
+    cache_k[bi, :, n[bi] + ii] = k.to(cache_k.dtype)[bi, :, ii]
+    cache_v[bi, :, n[bi] + ii] = v.to(cache_v.dtype)[bi, :, ii]
+    return o.permute(0, 2, 1, 3).reshape(B, T, num_heads * D).to(qkv_new.dtype)
+
+
+def attention_extend(qkv_new: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor, lens: torch.Tensor,
+                     num_heads: int, max_len: int, new_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Causal attention of a chunk of new tokens over the cache plus the chunk, with the append; returns
+    ``[B, T, H·D]``."""
+    _extend_guard(qkv_new, cache_k, cache_v, max_len)
+    if (_lib.use_native(qkv_new, cache_k, cache_v, lens, new_lens) and qkv_new.dtype == torch.bfloat16
+            and cache_k.dtype == torch.bfloat16 and cache_v.dtype == torch.bfloat16
+            and qkv_new.shape[2] == 3 * 64 * num_heads):
+        from . import _native_attn_extend
+        return _native_attn_extend.attention_extend(qkv_new, cache_k, cache_v, lens, num_heads, max_len, new_lens)
+    return attention_extend_reference(qkv_new, cache_k, cache_v, lens, num_heads, max_len, new_lens)
