@@ -816,8 +816,11 @@ def _choose(mode, A, lda, B, ldb, C, ldc, M, N, K, bias, act, aux, splits, conv,
         choice = _heuristic(mode, M, N, K, row_remap, lda, ldb)
     if colstats is not None and (choice[1] != 1 or choice[0].startswith("t")):
         choice = (choice[0] if choice[0] in ("big", "big192", "duo") else "small", 1)
-        if act == "dgelu" and choice[0] == "small" and _big_allowed(mode, K, lda, ldb):
-            choice = ("big", 1)        # dGELU column sums: register epilogues only
+    if colstats is not None and act == "dgelu" and choice[0] not in ("big", "big192", "duo") \
+            and _big_allowed(mode, K, lda, ldb):
+        # dGELU column sums: register epilogues only -- also when the heuristic (tuner off, graph capture)
+        # or a forced kind already names an unsplit 128-wide kernel, whose entry point refuses the pair
+        choice = ("big", 1)
     return choice
 
 

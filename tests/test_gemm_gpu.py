@@ -2,7 +2,9 @@
 
 Asymmetric random operands throughout (a transposed C-write cannot pass), odd
 shapes that exercise every M/N/K tail path, and every loader layout.
-"""
+
+Per-element numerics (an exact fp64 oracle, bitwise in its integer tier, guard bands and leading-dimension
+gaps) are checked in tests/test_gemm_oracle_gpu.py; this file keeps its coarser end-to-end checks."""
 import pytest
 import torch
 import torch.nn.functional as F

@@ -1,7 +1,10 @@
 """Streaming skinny GEMM (csrc/kernels/skinny_gemm.hip) against fp32 PyTorch: the ResNet
 stage-1 1x1 conv shapes (N, K) = (256, 64) and (64, 256) with their epilogues -- BatchNorm
 statistics rows, a residual, and the BatchNorm-backward reduction -- including an M that
-is not a multiple of the 64-row tile and grids that give workgroups several tiles."""
+is not a multiple of the 64-row tile and grids that give workgroups several tiles.
+
+Per-element numerics (an exact fp64 oracle, bitwise in its integer tier, guard bands and leading-dimension
+gaps) are checked in tests/test_gemm_oracle_gpu.py; this file keeps its coarser end-to-end checks."""
 import pytest
 import torch
 

@@ -2,7 +2,10 @@
 stage-2 1x1 conv shapes (N, K) = (512, 128) and (128, 512) with their epilogues -- BatchNorm
 statistics rows (forward), the BatchNorm-backward reduction (dgrad) and that plus the
 block-input residual -- including an M that is not a multiple of the tile, odd tile counts per
-workgroup (the two-tile unrolled loop's tail) and grids that give workgroups many tiles."""
+workgroup (the two-tile unrolled loop's tail) and grids that give workgroups many tiles.
+
+Per-element numerics (an exact fp64 oracle, bitwise in its integer tier, guard bands and leading-dimension
+gaps) are checked in tests/test_gemm_oracle_gpu.py; this file keeps its coarser end-to-end checks."""
 import pytest
 import torch
 
