@@ -83,7 +83,7 @@ class TrainConfig:
     def resolved_task(self) -> str:
         if self.task != "auto":
             return self.task
-        return "nlp" if self.model.startswith(("bert", "gpt")) else "cv"
+        return "nlp" if self.model.startswith(("bert", "gpt", "llama", "smollm")) else "cv"
 
     @property
     def resolved_optimizer(self) -> str:
@@ -91,7 +91,7 @@ class TrainConfig:
             return self.optimizer
         if self.model.startswith("bert_large"):
             return "lamb"
-        if self.model.startswith(("bert", "vit", "gpt")):
+        if self.model.startswith(("bert", "vit", "gpt", "llama", "smollm")):
             return "adamw"
         return "sgd"
 
@@ -179,6 +179,11 @@ PRESETS: Dict[str, TrainConfig] = {
     "gpt2_pretrain": TrainConfig(model="gpt2", batch_size=16, seq_len=1024, vocab_size=50257, dtype="bf16",
                                  optimizer="adamw", lr=6e-4, weight_decay=0.1, betas=[0.9, 0.95], eps=1e-8,
                                  dropout=0.1),
+    # SmolLM-135M (Llama family: RMSNorm, RoPE, grouped-query attention, SwiGLU) causal-LM pretraining at its
+    # full context (8 x 2048 tokens per GPU and step); the family has no dropout
+    "llama_pretrain": TrainConfig(model="smollm_135m", batch_size=8, seq_len=2048, vocab_size=49152, dtype="bf16",
+                                  optimizer="adamw", lr=3e-3, weight_decay=0.01, betas=[0.9, 0.95], eps=1e-8,
+                                  dropout=0.0),
 }
 
 

@@ -1,0 +1,257 @@
+"""Llama-family causal language model: RMSNorm, rotary positions, grouped-query attention, SwiGLU, no biases.
+
+Parameter-for-parameter equivalent to HF ``LlamaForCausalLM`` (SmolLM-135M: 134,515,008 parameters); the
+q / k / v projections are stored fused (``qkv``, rows ``[q | k | v]``) and so are gate / up (``gate_up``).
+The blocks are ``GPT2Block``'s no-dropout wiring -- residual adds in the output GEMMs' epilogues, the
+residual-stream gradient bridged into each RMSNorm backward -- with ``ops.rms_norm`` for the norms,
+``ops.rope_qkv`` between the projection and ``ops.attention(causal=True)`` (it rotates q and k and repeats each
+k / v head to its query heads, so the attention kernels see the packed ``[B, S, 3 H D]`` they were written for)
+and ``ops.swiglu`` between the two MLP GEMMs.  The head is the token embedding (tied) or a separate bias-free
+``lm_head`` and, with labels, the fused vocabulary head + loss (``ops.linear_cross_entropy``).
+
+Labels are NOT shifted here (the GPT-2 convention): ``labels[b, s]`` is the token at ``s + 1``.
+
+Head dimension 64 takes the native kernels; any other even head dimension runs through the references of
+``ops.rope_qkv`` and ``ops.attention``.  Not covered: generation (the decode / extend kernels append unrotated
+keys of an H-head projection to an H-head cache), ``rope_scaling``, sliding-window attention, biased
+projections.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import torch
+import torch.nn as nn
+
+from .. import ops
+from ..ops.bridge import GradBridge
+from .layers import Embedding, Linear
+
+
+@dataclass
+class LlamaConfig:
+    vocab_size: int = 49152
+    hidden_size: int = 576
+    intermediate_size: int = 1536
+    num_hidden_layers: int = 30
+    num_attention_heads: int = 9
+    num_key_value_heads: int = 3
+    max_position_embeddings: int = 2048
+    rms_norm_eps: float = 1e-5
+    rope_theta: float = 10000.0
+    tie_word_embeddings: bool = True
+    initializer_range: float = 0.02
+
+
+class RMSNorm(nn.Module):
+    def __init__(self, d: int, eps: float = 1e-5):
+        super().__init__()
+        self.d, self.eps = d, eps
+        self.weight = nn.Parameter(torch.ones(d))
+
+    def forward(self, x, grad_from=None):
+        return ops.rms_norm(x, self.weight, self.eps, grad_from=grad_from)
+
+    def extra_repr(self):
+        return f"{self.d}, eps={self.eps}"
+
+
+class LlamaBlock(nn.Module):
+    def __init__(self, c: LlamaConfig):
+        super().__init__()
+        E, std = c.hidden_size, c.initializer_range
+        self.num_heads, self.num_kv_heads = c.num_attention_heads, c.num_key_value_heads
+        D = E // self.num_heads
+        self.input_layernorm = RMSNorm(E, c.rms_norm_eps)
+        self.qkv = Linear(E, (self.num_heads + 2 * self.num_kv_heads) * D, bias=False, init_std=std)
+        self.o_proj = Linear(self.num_heads * D, E, bias=False, init_std=std)
+        self.post_attention_layernorm = RMSNorm(E, c.rms_norm_eps)
+        self.gate_up = Linear(E, 2 * c.intermediate_size, bias=False, init_std=std)
+        self.down_proj = Linear(c.intermediate_size, E, bias=False, init_std=std)
+
+    def forward(self, h, table, mask=None):
+        bridged = torch.is_grad_enabled() and h.requires_grad
+        b1 = GradBridge() if bridged else None
+        y = self.input_layernorm(h, grad_from=b1)
+        qkv = ops.rope_qkv(self.qkv(y), table, self.num_heads, self.num_kv_heads)
+        ctx = ops.attention(qkv, self.num_heads, mask, 0.0, self.training, causal=True)
+        h = self.o_proj(ctx, residual=h, residual_grad_to=b1)
+        b2 = GradBridge() if bridged else None
+        y = self.post_attention_layernorm(h, grad_from=b2)
+        return self.down_proj(ops.swiglu(self.gate_up(y)), residual=h, residual_grad_to=b2)
+
+
+class LlamaForCausalLM(nn.Module):
+    def __init__(self, c: LlamaConfig):
+        super().__init__()
+        if c.hidden_size % c.num_attention_heads:
+            raise ValueError("hidden_size must be a multiple of num_attention_heads")
+        if c.num_key_value_heads < 1 or c.num_attention_heads % c.num_key_value_heads:
+            raise ValueError("num_attention_heads must be a multiple of num_key_value_heads")
+        D = c.hidden_size // c.num_attention_heads
+        if D % 2:
+            raise ValueError("the head dimension must be even (rotary pairs)")
+        self.config = c
+        self.embed_tokens = Embedding(c.vocab_size, c.hidden_size, c.initializer_range)
+        self.layers = nn.ModuleList([LlamaBlock(c) for _ in range(c.num_hidden_layers)])
+        self.norm = RMSNorm(c.hidden_size, c.rms_norm_eps)
+        self.lm_head = None
+        if not c.tie_word_embeddings:
+            self.lm_head = Linear(c.hidden_size, c.vocab_size, bias=False, init_std=c.initializer_range)
+        self.register_buffer("rope_table", ops.rope_table(c.max_position_embeddings, c.rope_theta, D),
+                             persistent=False)
+
+    # ZeRO-1 gather waits (parallel/ddp.py): the root's forward reads the embedding and the head's weight
+    # directly
+    @property
+    def _ddl_direct_reads(self):
+        return ("embed_tokens",) if self.lm_head is None else ("embed_tokens", "lm_head")
+
+    def _apply(self, fn, recurse=True):
+        # the rotary table stays fp32 when the module is cast to bf16
+        super()._apply(fn, recurse)
+        if self.rope_table.dtype != torch.float32:
+            c = self.config
+            self.rope_table = ops.rope_table(c.max_position_embeddings, c.rope_theta,
+                                             c.hidden_size // c.num_attention_heads, self.rope_table.device)
+        return self
+
+    def head_weight(self) -> torch.Tensor:
+        return self.embed_tokens.weight if self.lm_head is None else self.lm_head.weight
+
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None):
+        """``token_type_ids`` is ignored: it keeps the training loop's ``(input_ids, attention_mask,
+        token_type_ids, labels)`` call form.  Returns ``(loss, None)`` with labels -- the fused head never
+        hands out the logits -- and the ``[B, S, vocab]`` logits without."""
+        B, S = input_ids.shape
+        if S > self.config.max_position_embeddings:
+            raise ValueError(f"sequence length {S} exceeds max_position_embeddings "
+                             f"{self.config.max_position_embeddings}")
+        mask_bias = None
+        if attention_mask is not None:
+            mask_bias = (1.0 - attention_mask.float()) * -10000.0
+        h = self.embed_tokens(input_ids)
+        for blk in self.layers:
+            h = blk(h, self.rope_table, mask_bias)
+        h = self.norm(h)
+        w = self.head_weight()
+        if labels is not None:
+            loss = ops.linear_cross_entropy(h.reshape(-1, h.shape[-1]), w, None, labels.reshape(-1), -100,
+                                            defer_weight_ready=self.lm_head is None)
+            return loss, None
+        return ops.linear(h, w, None)
+
+
+def _make(**kw) -> LlamaForCausalLM:
+    return LlamaForCausalLM(LlamaConfig(**kw))
+
+
+def llama_tiny(**kw) -> LlamaForCausalLM:
+    """2 layers, hidden 128, 2 heads over 1 KV head (head dim 64), vocabulary 1000: the code path at test size."""
+    d = dict(hidden_size=128, num_hidden_layers=2, num_attention_heads=2, num_key_value_heads=1,
+             intermediate_size=352, vocab_size=1000, max_position_embeddings=256)
+    d.update(kw)
+    return _make(**d)
+
+
+def smollm_135m(**kw) -> LlamaForCausalLM:
+    return _make(**kw)
+
+
+def smollm_360m(**kw) -> LlamaForCausalLM:
+    d = dict(hidden_size=960, num_hidden_layers=32, num_attention_heads=15, num_key_value_heads=5,
+             intermediate_size=2560)
+    d.update(kw)
+    return _make(**d)
+
+
+def smollm_1p7b(**kw) -> LlamaForCausalLM:
+    d = dict(hidden_size=2048, num_hidden_layers=24, num_attention_heads=32, num_key_value_heads=32,
+             intermediate_size=8192)
+    d.update(kw)
+    return _make(**d)
+
+
+# ------------------------------------------------------------ HF conversion
+# HF keeps q_proj / k_proj / v_proj and gate_proj / up_proj apart ([out, in] each, as here): their rows
+# concatenate into ``qkv.weight`` and ``gate_up.weight``.
+_HF_SAME = {"self_attn.o_proj": "o_proj", "mlp.down_proj": "down_proj", "input_layernorm": "input_layernorm",
+            "post_attention_layernorm": "post_attention_layernorm"}
+
+
+def check_hf_config(hf_config) -> None:
+    """Raises ``ValueError`` for an HF ``LlamaConfig`` (object or dict) this model does not cover."""
+    get = _getter(hf_config)
+    # (recent HF versions keep rope_theta in the same dict, with rope_type "default": that is no scaling)
+    scaling = get("rope_scaling") or get("rope_parameters")
+    if scaling is not None:
+        kind = scaling.get("rope_type", scaling.get("type"))
+        if kind not in (None, "default") or "factor" in scaling:
+            raise ValueError(f"rope_scaling ({kind}) is not supported")
+    if get("attention_bias", False) or get("mlp_bias", False):
+        raise ValueError("biased projections (attention_bias / mlp_bias) are not supported")
+
+
+def _getter(hf_config):
+    return hf_config.get if isinstance(hf_config, dict) else (lambda k, d=None: getattr(hf_config, k, d))
+
+
+def config_from_hf(hf_config) -> LlamaConfig:
+    """This model's config from an HF ``LlamaConfig`` (object, or the dict of its ``config.json``)."""
+    check_hf_config(hf_config)
+    get = _getter(hf_config)
+    E, H = get("hidden_size"), get("num_attention_heads")
+    if get("head_dim") not in (None, E // H):
+        raise ValueError("head_dim must be hidden_size / num_attention_heads")
+    theta = get("rope_theta")
+    if theta is None:
+        theta = (get("rope_parameters") or get("rope_scaling") or {}).get("rope_theta", 10000.0)
+    return LlamaConfig(vocab_size=get("vocab_size"), hidden_size=E, intermediate_size=get("intermediate_size"),
+                       num_hidden_layers=get("num_hidden_layers"), num_attention_heads=H,
+                       num_key_value_heads=get("num_key_value_heads") or H,
+                       max_position_embeddings=get("max_position_embeddings"), rms_norm_eps=get("rms_norm_eps"),
+                       rope_theta=float(theta), tie_word_embeddings=bool(get("tie_word_embeddings", False)),
+                       initializer_range=get("initializer_range", 0.02))
+
+
+def from_hf_state_dict(sd: dict, config: LlamaConfig, hf_config=None) -> dict:
+    """HF ``LlamaForCausalLM`` state dict -> this model's (``config``: this model's)."""
+    if hf_config is not None:
+        check_hf_config(hf_config)
+    if any(k.endswith(".bias") for k in sd):
+        raise ValueError("biased projections (attention_bias / mlp_bias) are not supported")
+    emb = sd["model.embed_tokens.weight"]
+    head = sd.get("lm_head.weight")
+    out = {"embed_tokens.weight": emb, "norm.weight": sd["model.norm.weight"]}
+    if config.tie_word_embeddings:
+        if head is not None and not torch.equal(head, emb):
+            raise ValueError("tie_word_embeddings is set but lm_head.weight differs from model.embed_tokens.weight")
+    else:
+        if head is None:
+            raise ValueError("tie_word_embeddings is not set but the state dict has no lm_head.weight")
+        out["lm_head.weight"] = head
+    for i in range(config.num_hidden_layers):
+        p, o = f"model.layers.{i}.", f"layers.{i}."
+        out[o + "qkv.weight"] = torch.cat([sd[p + f"self_attn.{n}_proj.weight"] for n in "qkv"], 0)
+        out[o + "gate_up.weight"] = torch.cat([sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"]], 0)
+        for hf, ours in _HF_SAME.items():
+            out[o + ours + ".weight"] = sd[p + hf + ".weight"]
+    return out
+
+
+def to_hf_state_dict(sd: dict, config: LlamaConfig) -> dict:
+    c = config
+    D = c.hidden_size // c.num_attention_heads
+    nq, nkv = c.num_attention_heads * D, c.num_key_value_heads * D
+    out = {"model.embed_tokens.weight": sd["embed_tokens.weight"], "model.norm.weight": sd["norm.weight"],
+           "lm_head.weight": sd["embed_tokens.weight"] if c.tie_word_embeddings else sd["lm_head.weight"]}
+    for i in range(c.num_hidden_layers):
+        p, o = f"model.layers.{i}.", f"layers.{i}."
+        q, k, v = sd[o + "qkv.weight"].split([nq, nkv, nkv], 0)
+        out[p + "self_attn.q_proj.weight"], out[p + "self_attn.k_proj.weight"] = q.contiguous(), k.contiguous()
+        out[p + "self_attn.v_proj.weight"] = v.contiguous()
+        g, u = sd[o + "gate_up.weight"].chunk(2, 0)
+        out[p + "mlp.gate_proj.weight"], out[p + "mlp.up_proj.weight"] = g.contiguous(), u.contiguous()
+        for hf, ours in _HF_SAME.items():
+            out[p + hf + ".weight"] = sd[o + ours + ".weight"]
+    return out

@@ -22,3 +22,4 @@ from .pool import max_pool2d, global_avg_pool  # noqa: F401
 from .embedding import embedding  # noqa: F401
 from .mlm import gather_rows, linear_cross_entropy  # noqa: F401
 from .glue import embedding_residual, first_token, prepend_token_add  # noqa: F401
+from .llama import rms_norm, rope_table, rope_qkv, swiglu  # noqa: F401

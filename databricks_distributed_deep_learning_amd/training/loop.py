@@ -154,7 +154,7 @@ class Trainer:
         vocab = min(c.vocab_size, getattr(mc, "vocab_size", c.vocab_size))
         return SyntheticTokens(c.batch_size, c.seq_len, vocab, c.num_classes, self.device,
                                rank=self.rank, seed=c.seed, pool=c.synthetic_pool, pad_fraction=c.pad_fraction,
-                               mlm_predictions=c.mlm_predictions, causal_lm=c.model.startswith("gpt"))
+                               mlm_predictions=c.mlm_predictions, causal_lm=c.model.startswith(("gpt", "llama", "smollm")))
 
     def _auto_batch(self) -> int:
         from ..utils.memory import fit_batch_size
@@ -305,7 +305,7 @@ class Trainer:
         # untuned GEMM signatures of transformer models pick their kernels from their own calls in
         # these warm-up steps (ops/_native_gemm.py online_tuning; DDL_GEMM_TUNE_ONLINE=0/1 overrides)
         from ..ops import _native_gemm
-        transformer = c.model.startswith(("bert", "vit", "gpt", "t5", "roberta"))
+        transformer = c.model.startswith(("bert", "vit", "gpt", "llama", "smollm", "t5", "roberta"))
         online_mb = float(os.environ.get("DDL_GEMM_ONLINE_MAX_MB", "inf" if transformer else "0"))
         with _native_gemm.online_tuning(enabled=self.device.type == "cuda", default=online_mb > 0,
                                         max_mb=online_mb):

@@ -7,6 +7,8 @@ last ``v_mfma`` of the densest cluster).  Exits 1 if any main loop holds more th
 
     python scripts/check_spills.py                      # compile csrc/kernels/gemm_big.hip
     python scripts/check_spills.py --asm /tmp/gb.s      # scan an existing assembly file
+    python scripts/check_spills.py --all-kernels --src csrc/kernels/llama.hip
+                                                        # every kernel of a source: exits 1 on any scratch use
 """
 import argparse
 import os
@@ -57,17 +59,36 @@ def scan(text: str):
     return rows
 
 
+ANY = re.compile(r"\n(\w+):[^\n]*\n(.*?)\.Lfunc_end", re.S)
+META = re.compile(r"\.name:\s+(\w+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)")
+
+
+def scan_all(text: str):
+    """(kernel, scratch instructions, private segment bytes) of every kernel in the assembly."""
+    priv = {m.group(1): int(m.group(2)) for m in META.finditer(text)}
+    return [(m.group(1), sum("scratch_" in ln for ln in m.group(2).split("\n")), priv[m.group(1)])
+            for m in ANY.finditer(text) if m.group(1) in priv]
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--asm", default="")
     ap.add_argument("--src", default=os.path.join(ROOT, "csrc", "kernels", "gemm_big.hip"))
     ap.add_argument("-D", dest="defines", action="append", default=[])
     ap.add_argument("--max-loop", type=int, default=16)
+    ap.add_argument("--all-kernels", action="store_true")
     a = ap.parse_args()
     path = a.asm
     if not path:
         path = os.path.join(tempfile.mkdtemp(), "k.s")
         emit(a.src, path, a.defines)
+    if a.all_kernels:
+        with open(path) as f:
+            rows = scan_all(f.read())
+        print("kernel  scratch-instructions  private-segment-bytes")
+        for name, nsc, nb in rows:
+            print(f"{name} {nsc} {nb}{'  <-- scratch' if nsc or nb else ''}")
+        return 1 if not rows or any(nsc or nb for _, nsc, nb in rows) else 0
     with open(path) as f:
         rows = scan(f.read())
     bad = 0
