@@ -9,6 +9,7 @@ from .bert import BertConfig, BertForSequenceClassification, bert_base, bert_lar
 from .bert import BertForPreTraining, bert_base_pretraining, bert_large_pretraining, bert_tiny_pretraining  # noqa: F401
 from .vit import ViTConfig, ViTForImageClassification, vit_b16  # noqa: F401
 from .gpt2 import GPT2Config, GPT2LMHeadModel, KVCache, gpt2, gpt2_medium, gpt2_large, gpt2_tiny  # noqa: F401
+from .llama import LlamaKVCache  # noqa: F401
 from .llama import LlamaConfig, LlamaForCausalLM, llama_tiny, smollm_135m, smollm_360m, smollm_1p7b  # noqa: F401
 from .layers import cast_params, convert_sync_batchnorm  # noqa: F401
 

@@ -1,11 +1,16 @@
-"""A GPT-2 decode session: the static state of a generation loop and its step, captured once.
+"""A decode session: the static state of a generation loop and its step, captured once.
 
-The step is one linear chain on one stream -- ``ops.decode_embed``, every block's ``decode`` with the
-attention launch bound fixed at the cache capacity (so the grid is the same at every step; rows past
-``lens`` are still never loaded), ``ln_f``, the head ``ops.linear_small_m`` and ``ops.next_token``, which
-also advances the cache lengths and the step counter -- and it reads and writes only the session's own
+The step is one linear chain on one stream -- the model's ``_session_logits`` (GPT-2: ``ops.decode_embed``,
+every block's ``decode``, ``ln_f`` and the head ``ops.linear_small_m``; Llama: the ``embed_tokens`` gather,
+every block's ``decode``, ``norm`` and the head), with the attention launch bound fixed at the cache capacity
+(so the grid is the same at every step; rows past ``lens`` are still never loaded), then ``ops.next_token``,
+which also advances the cache lengths and the step counter -- and it reads and writes only the session's own
 tensors, so on the GPU it is captured into a ``torch.cuda.CUDAGraph`` and replayed: one host call per token
 instead of about a hundred.  Off the GPU (or without the native kernels) the same step runs eagerly.
+
+What a model hands the session: ``_session_weight()`` (its token embedding: device and dtype of the
+state, part of the key), ``_session_cache(batch, capacity, device)`` and ``_session_logits(tok_cur, cache)``
+(the step up to the ``[B, vocab]`` logits, at ``len_bound = cache.capacity``, not advancing the lengths).
 """
 from __future__ import annotations
 
@@ -24,7 +29,7 @@ def round_capacity(need: int, n_positions: int) -> int:
 
 
 def _key(model, batch: int, capacity: int, graph: bool):
-    w = model.wte.weight
+    w = model._session_weight()
     return (batch, capacity, w.device, w.dtype, graph, tuple(p.data_ptr() for p in model.parameters()))
 
 
@@ -48,12 +53,11 @@ class DecodeSession:
     WARMUP = 2
 
     def __init__(self, model, batch: int, capacity: int, graph: bool, key=None):
-        from .gpt2 import KVCache
-        dev = model.wte.weight.device
+        dev = model._session_weight().device
         self.key = key
         self._model = weakref.ref(model)
         self.batch, self.capacity = batch, capacity
-        self.cache = KVCache.allocate(model, batch, capacity, dev)
+        self.cache = model._session_cache(batch, capacity, dev)
         self.tok_cur = torch.zeros(batch, dtype=torch.int64, device=dev)
         self.done = torch.zeros(batch, dtype=torch.bool, device=dev)
         self.step = torch.zeros(batch, dtype=torch.int32, device=dev)
@@ -69,13 +73,9 @@ class DecodeSession:
         return (self.cache.lens, self.tok_cur, self.done, self.step, self.tokens_out)
 
     def _step(self):
-        m, c = self._model(), self.cache
-        h = ops.decode_embed(self.tok_cur, c.lens, m.wte.weight, m.wpe.weight)
-        for i, blk in enumerate(m.h):
-            h = blk.decode(h, c, i, len_bound=c.capacity)
-        logits = ops.linear_small_m(m.ln_f(h), m.wte.weight, None)
+        logits = self._model()._session_logits(self.tok_cur, self.cache)
         ops.next_token(logits, u=self.u, params=self.params, step=self.step, done=self.done, out=self.tok_cur,
-                       tokens_out=self.tokens_out, lens=c.lens)
+                       tokens_out=self.tokens_out, lens=self.cache.lens)
 
     def _capture(self):
         # the warm-up really executes (on a side stream, as export.GraphRunner's): it writes dead cache rows,

@@ -44,6 +44,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..ops.bridge import GradBridge
+from . import _generate as G
 from .layers import Dropout, Embedding, LayerNorm, Linear
 
 
@@ -360,70 +361,36 @@ class GPT2LMHeadModel(nn.Module):
         prompt is consumed in chunks of that many columns through ``extend`` (the first one included), which
         bounds the prompt's activations by the chunk.  Without either, the prompt goes through ``prefill``."""
         B, S_in = input_ids.shape
-        if max_new_tokens < 1:
-            raise ValueError("max_new_tokens must be at least 1")
+        G.check_sampling(max_new_tokens, do_sample, temperature, top_k)
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError("prefill_chunk must be at least 1")
         P0 = 0 if prefix is None else prefix.max_len
         if P0 + S_in + max_new_tokens > self.config.n_positions:
             raise ValueError(f"{'prefix + ' if prefix is not None else ''}S_in + max_new_tokens = "
                              f"{P0 + S_in + max_new_tokens} exceeds n_positions {self.config.n_positions}")
-        if do_sample and not temperature > 0:
-            raise ValueError("temperature must be positive")
-        if top_k is not None and top_k < 1:
-            raise ValueError("top_k must be at least 1")
         dev = input_ids.device
-        ar = torch.arange(S_in, device=dev)[None, :]
-        if attention_mask is None:
-            ids, cnt, S0 = input_ids, torch.full((B,), S_in, dtype=torch.int32, device=dev), S_in
-        else:
-            m = attention_mask.to(dev) != 0
-            cnt = m.sum(1)
-            first = m.int().argmax(1)
-            run = (ar >= first[:, None]) & (ar < (first + cnt)[:, None])
-            if not bool(((run == m).all(1) & (cnt > 0)).all()):
-                raise ValueError("each attention_mask row must be one contiguous, non-empty run of ones")
-            # compact to right-padded: row b's tokens move to columns 0 .. cnt[b]-1
-            ids = input_ids.gather(1, (first[:, None] + ar).clamp(max=S_in - 1))
-            ids = torch.where(ar < cnt[:, None], ids, torch.zeros_like(ids))
-            S0 = int(cnt.max())
-            ids, cnt = ids[:, :S0].contiguous(), cnt.int()
+        ids, cnt, S0 = G.compact_prompts(input_ids, attention_mask)
         if pad_token_id is None:
             pad_token_id = eos_token_id
+        need = P0 + S0 + max_new_tokens
         was_training = self.training
         self.eval()
-        if use_graph:
-            try:
-                new = self._generate_session(ids, cnt, P0 + S0 + max_new_tokens, max_new_tokens, do_sample,
-                                             temperature, top_k, eos_token_id, pad_token_id, generator, prefix,
-                                             prefill_chunk)
-            finally:
-                self.train(was_training)
-            return torch.cat([input_ids, new.to(input_ids.dtype)], 1)
         try:
-            cache = KVCache.allocate(self, B, P0 + S0 + max_new_tokens, dev)
-            logits = self._consume_prompt(ids, cnt, cache, prefix, prefill_chunk)
-            done = torch.zeros(B, dtype=torch.bool, device=dev)
-            new = []
-            for i in range(max_new_tokens):
-                if do_sample:
-                    z = logits.float() / temperature
-                    if top_k is not None and top_k < z.shape[-1]:
-                        kth = z.topk(top_k, -1).values[:, -1:]
-                        z = torch.where(z < kth, torch.full_like(z, float("-inf")), z)
-                    tok = torch.multinomial(torch.softmax(z, -1), 1, generator=generator).squeeze(1)
-                else:
-                    tok = logits.argmax(-1)
-                if eos_token_id is not None:
-                    tok = torch.where(done, torch.full_like(tok, pad_token_id), tok)
-                    done = done | (tok == eos_token_id)
-                new.append(tok)
-                if i + 1 == max_new_tokens or (eos_token_id is not None and bool(done.all())):
-                    break
-                logits = self.decode_step(tok, cache)       # finished rows keep decoding (on pad tokens)
+            if use_graph:
+                from ._decode_graph import round_capacity, session_for
+                sess = session_for(self, B, round_capacity(need, self.config.n_positions),
+                                   G.use_graph_for(self.wte.weight))
+                new = G.session_loop(sess, lambda cache: self._consume_prompt(ids, cnt, cache, prefix, prefill_chunk),
+                                     B, dev, max_new_tokens, do_sample, temperature, top_k, eos_token_id,
+                                     pad_token_id, generator)
+            else:
+                cache = KVCache.allocate(self, B, need, dev)
+                logits = self._consume_prompt(ids, cnt, cache, prefix, prefill_chunk)
+                new = G.token_loop(logits, lambda tok: self.decode_step(tok, cache), max_new_tokens, do_sample,
+                                   temperature, top_k, eos_token_id, pad_token_id, generator)
         finally:
             self.train(was_training)
-        return torch.cat([input_ids, torch.stack(new, 1).to(input_ids.dtype)], 1)
+        return torch.cat([input_ids, new.to(input_ids.dtype)], 1)
 
     @property
     def decode_session(self):
@@ -431,34 +398,18 @@ class GPT2LMHeadModel(nn.Module):
         from ._decode_graph import current_session
         return current_session(self)
 
-    def _generate_session(self, ids, cnt, need, max_new_tokens, do_sample, temperature, top_k, eos_token_id,
-                          pad_token_id, generator, prefix=None, prefill_chunk=None):
-        """``generate``'s loop on a decode session -> the new tokens ``[B, n_new]``."""
-        from ..ops import _lib
-        from ._decode_graph import round_capacity, session_for
-        B, dev, w = ids.shape[0], ids.device, self.wte.weight
-        graph = dev.type == "cuda" and w.dtype == torch.bfloat16 and _lib.use_native(w)
-        sess = session_for(self, B, round_capacity(need, self.config.n_positions), graph)
-        u = None
-        if do_sample:
-            u = torch.rand(max_new_tokens, B, generator=generator,
-                           device=dev if generator is None else generator.device).to(dev)
-        sess.begin(ops.next_token_params(1.0 / temperature if do_sample else 1.0, top_k, eos_token_id, pad_token_id,
-                                         do_sample, dev), u)
-        sess.first_token(self._consume_prompt(ids, cnt, sess.cache, prefix, prefill_chunk))
-        n = 1
-        while n < max_new_tokens:
-            sess.advance()
-            n += 1
-            if eos_token_id is not None and n % 16 == 0 and bool(sess.done.all()):
-                break
-        new = sess.tokens_out[:, :n].clone()
-        if eos_token_id is not None:
-            # what the per-step check returns: through the step in which the last row emitted eos
-            is_eos = new == eos_token_id
-            if bool(is_eos.any(1).all()):
-                new = new[:, :int(is_eos.int().argmax(1).max()) + 1]
-        return new
+    # what a decode session (models/_decode_graph.py) asks of its model
+    def _session_weight(self):
+        return self.wte.weight
+
+    def _session_cache(self, batch, capacity, device):
+        return KVCache.allocate(self, batch, capacity, device)
+
+    def _session_logits(self, tok_cur, cache: KVCache):
+        h = ops.decode_embed(tok_cur, cache.lens, self.wte.weight, self.wpe.weight)
+        for i, blk in enumerate(self.h):
+            h = blk.decode(h, cache, i, len_bound=cache.capacity)
+        return ops.linear_small_m(self.ln_f(h), self.wte.weight, None)
 
 
 def _make(dropout: float, activation_function: str, **kw) -> GPT2LMHeadModel:

@@ -12,9 +12,19 @@ and ``ops.swiglu`` between the two MLP GEMMs.  The head is the token embedding (
 Labels are NOT shifted here (the GPT-2 convention): ``labels[b, s]`` is the token at ``s + 1``.
 
 Head dimension 64 takes the native kernels; any other even head dimension runs through the references of
-``ops.rope_qkv`` and ``ops.attention``.  Not covered: generation (the decode / extend kernels append unrotated
-keys of an H-head projection to an H-head cache), ``rope_scaling``, sliding-window attention, biased
-projections.
+``ops.rope_qkv`` and ``ops.attention``.
+
+Generation (``generate``, GPT-2's contract): ``prefill`` runs the causal forward once over the right-padded
+prompts, copies every layer's rotated keys and its values into a ``LlamaKVCache`` -- ``[L, 2, B, Hkv, C, D]``:
+the Hkv key / value heads, never expanded to the H query heads -- and applies the head to each sequence's last
+row only; ``decode_step`` then feeds one token per sequence through ``LlamaBlock.decode``: the M <= 16
+weight-streaming linears (``ops.linear_small_m``) and ``ops.attention_decode_gqa``, which rotates the new
+token's queries and key by the row's own position, scores every cached row once against the G query heads of
+its group and appends.  ``generate(use_graph=True)`` runs the step from a decode session
+(``models/_decode_graph.py``): captured once into a hipGraph and replayed per token.
+
+Not covered: ``extend`` (``prefix=`` / ``prefill_chunk=``) for this family, ``rope_scaling``, sliding-window
+attention, biased projections.
 """
 from __future__ import annotations
 
@@ -25,6 +35,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..ops.bridge import GradBridge
+from . import _generate as G
 from .layers import Embedding, Linear
 
 
@@ -56,6 +67,37 @@ class RMSNorm(nn.Module):
         return f"{self.d}, eps={self.eps}"
 
 
+class LlamaKVCache:
+    """Rotated keys and values of every layer, ``data [L, 2, B, Hkv, C, D]`` (C: capacity in positions), the
+    valid length of each batch row on the device (``lens``, int32 ``[B]``) and ``max_len``, the host's upper
+    bound on ``lens`` -- what sizes the decode launches, so no step reads ``lens`` back."""
+
+    def __init__(self, data: torch.Tensor, lens: torch.Tensor):
+        self.data, self.lens = data, lens
+        self.capacity = data.shape[4]
+        self.max_len = 0
+
+    @classmethod
+    def allocate(cls, model: "LlamaForCausalLM", batch: int, capacity: int, device=None,
+                 dtype=None) -> "LlamaKVCache":
+        c = model.config
+        if not 1 <= capacity <= c.max_position_embeddings:
+            raise ValueError(f"capacity {capacity} must be in 1 .. max_position_embeddings "
+                             f"({c.max_position_embeddings})")
+        w = model.embed_tokens.weight
+        device = w.device if device is None else device
+        data = torch.empty(c.num_hidden_layers, 2, batch, c.num_key_value_heads, capacity,
+                           c.hidden_size // c.num_attention_heads, dtype=w.dtype if dtype is None else dtype,
+                           device=device)
+        return cls(data, torch.zeros(batch, dtype=torch.int32, device=device))
+
+    def k(self, layer: int) -> torch.Tensor:
+        return self.data[layer, 0]
+
+    def v(self, layer: int) -> torch.Tensor:
+        return self.data[layer, 1]
+
+
 class LlamaBlock(nn.Module):
     def __init__(self, c: LlamaConfig):
         super().__init__()
@@ -79,6 +121,25 @@ class LlamaBlock(nn.Module):
         b2 = GradBridge() if bridged else None
         y = self.post_attention_layernorm(h, grad_from=b2)
         return self.down_proj(ops.swiglu(self.gate_up(y)), residual=h, residual_grad_to=b2)
+
+    def prefill(self, h, table, mask, cache: LlamaKVCache, layer: int):
+        """The inference forward that also copies this layer's rotated keys and its values into the cache."""
+        qkv = ops.rope_qkv(self.qkv(self.input_layernorm(h)), table, self.num_heads, self.num_kv_heads)
+        ops.kv_cache_fill_gqa(qkv, cache.k(layer), cache.v(layer), self.num_heads, self.num_kv_heads)
+        h = self.o_proj(ops.attention(qkv, self.num_heads, mask, 0.0, False, causal=True), residual=h)
+        return self.down_proj(ops.swiglu(self.gate_up(self.post_attention_layernorm(h))), residual=h)
+
+    def decode(self, h_new, table, cache: LlamaKVCache, layer: int, len_bound=None):
+        """One new token per sequence, ``h_new [B, E]``, against the cache (which gains its rotated key and
+        its value).  ``len_bound``: the bound on ``lens + 1`` that sizes the attention launch (default
+        ``max_len + 1``)."""
+        lin = ops.linear_small_m
+        qkv = lin(self.input_layernorm(h_new), self.qkv.weight, None)
+        ctx = ops.attention_decode_gqa(qkv, table, cache.k(layer), cache.v(layer), cache.lens, self.num_heads,
+                                       self.num_kv_heads, cache.max_len + 1 if len_bound is None else len_bound)
+        h = lin(ctx, self.o_proj.weight, None, residual=h_new)
+        z = ops.swiglu(lin(self.post_attention_layernorm(h), self.gate_up.weight, None))
+        return lin(z, self.down_proj.weight, None, residual=h)
 
 
 class LlamaForCausalLM(nn.Module):
@@ -140,6 +201,114 @@ class LlamaForCausalLM(nn.Module):
                                             defer_weight_ready=self.lm_head is None)
             return loss, None
         return ops.linear(h, w, None)
+
+    # ------------------------------------------------------------ generation
+    def prefill(self, input_ids, lens, cache: LlamaKVCache):
+        """Right-padded prompts ``[B, S]`` of lengths ``lens`` (int ``[B]``, on the device) -> the next-token
+        logits ``[B, vocab]`` of each sequence's last token; fills ``cache`` and sets its lengths.  The head
+        runs on those B rows only: the ``[B, S, vocab]`` logits never exist."""
+        B, S = input_ids.shape
+        if S > cache.capacity:
+            raise ValueError(f"prompt length {S} exceeds the cache capacity {cache.capacity}")
+        with torch.no_grad():
+            lens = lens.to(device=input_ids.device, dtype=torch.int32)
+            keep = torch.arange(S, device=input_ids.device)[None, :] < lens[:, None]
+            mask_bias = (1.0 - keep.float()) * -10000.0
+            h = self.embed_tokens(input_ids)
+            for i, blk in enumerate(self.layers):
+                h = blk.prefill(h, self.rope_table, mask_bias, cache, i)
+            last = h[torch.arange(B, device=h.device), (lens - 1).long()]
+            cache.lens.copy_(lens)
+            cache.max_len = S
+            return ops.linear_small_m(self.norm(last), self.head_weight(), None)
+
+    def decode_step(self, tokens, cache: LlamaKVCache, len_bound=None):
+        """``tokens [B]``: the token at position ``cache.lens`` of each sequence -> the next-token logits
+        ``[B, vocab]``.  Every layer appends to the cache; the lengths advance once, after the last.
+        ``len_bound`` (default ``cache.max_len + 1``): the bound on ``lens + 1`` handed to the attention
+        launches; with ``cache.capacity`` every step launches the same grid (positions past ``lens`` are
+        still never loaded)."""
+        if cache.max_len + 1 > cache.capacity:
+            raise ValueError(f"max_len {cache.max_len + 1} exceeds the cache capacity {cache.capacity}")
+        if len_bound is not None and not cache.max_len + 1 <= len_bound <= cache.capacity:
+            raise ValueError(f"len_bound {len_bound} must be in max_len + 1 ({cache.max_len + 1}) .. the cache "
+                             f"capacity ({cache.capacity})")
+        with torch.no_grad():
+            logits = self._step_logits(tokens, cache, len_bound)
+            cache.lens += 1
+            cache.max_len += 1
+            return logits
+
+    def _step_logits(self, tokens, cache: LlamaKVCache, len_bound):
+        h = self.embed_tokens(tokens)
+        for i, blk in enumerate(self.layers):
+            h = blk.decode(h, self.rope_table, cache, i, len_bound)
+        return ops.linear_small_m(self.norm(h), self.head_weight(), None)
+
+    @torch.no_grad()
+    def generate(self, input_ids, attention_mask=None, max_new_tokens: int = 20, do_sample: bool = False,
+                 temperature: float = 1.0, top_k=None, eos_token_id=None, pad_token_id=None, generator=None,
+                 use_graph: bool = False):
+        """Greedy (argmax) or sampled (temperature, then top-k, then multinomial) continuation of
+        ``input_ids [B, S_in]`` -> ``[B, S_in + n_new]``: ``GPT2LMHeadModel.generate``'s contract.  Each row
+        as given, then its generated tokens, with ``pad_token_id`` (default ``eos_token_id``) after the first
+        ``eos_token_id``.  ``attention_mask`` rows must each be one contiguous run of ones (left- or
+        right-padded); the prompts are compacted to right-padded, so row b's rotary positions start at 0 --
+        what HF's ``position_ids`` from the mask give.  Always eval semantics.  Stops early once every row has
+        produced ``eos_token_id``: that check is the only host sync of a step and is made only when
+        ``eos_token_id`` is given.
+
+        ``use_graph=True``: the decode step runs from a session cached on the model
+        (``models/_decode_graph.py``): state on the device, tokens chosen by ``ops.next_token``, and on a GPU
+        with the native kernels and bf16 parameters the whole step is one captured graph, replayed once per
+        token (captured on the first call of a shape; rebuilt when the batch, the rounded cache capacity or a
+        parameter's storage changes).  Elsewhere the same loop runs eagerly.  Greedy output equals
+        ``use_graph=False``'s; with ``do_sample`` the tokens follow ``ops.next_token``'s definition from one
+        ``torch.rand(max_new_tokens, B, generator=generator)`` drawn before the loop.  The eos check syncs
+        only every 16 steps; the result is trimmed to the length ``use_graph=False`` returns."""
+        B, S_in = input_ids.shape
+        G.check_sampling(max_new_tokens, do_sample, temperature, top_k)
+        n_pos = self.config.max_position_embeddings
+        if S_in + max_new_tokens > n_pos:
+            raise ValueError(f"S_in + max_new_tokens = {S_in + max_new_tokens} exceeds max_position_embeddings "
+                             f"{n_pos}")
+        dev = input_ids.device
+        ids, cnt, S0 = G.compact_prompts(input_ids, attention_mask)
+        if pad_token_id is None:
+            pad_token_id = eos_token_id
+        was_training = self.training
+        self.eval()
+        try:
+            if use_graph:
+                from ._decode_graph import round_capacity, session_for
+                sess = session_for(self, B, round_capacity(S0 + max_new_tokens, n_pos),
+                                   G.use_graph_for(self.embed_tokens.weight))
+                new = G.session_loop(sess, lambda cache: self.prefill(ids, cnt, cache), B, dev, max_new_tokens,
+                                     do_sample, temperature, top_k, eos_token_id, pad_token_id, generator)
+            else:
+                cache = LlamaKVCache.allocate(self, B, S0 + max_new_tokens, dev)
+                new = G.token_loop(self.prefill(ids, cnt, cache), lambda tok: self.decode_step(tok, cache),
+                                   max_new_tokens, do_sample, temperature, top_k, eos_token_id, pad_token_id,
+                                   generator)
+        finally:
+            self.train(was_training)
+        return torch.cat([input_ids, new.to(input_ids.dtype)], 1)
+
+    @property
+    def decode_session(self):
+        """The session ``generate(use_graph=True)`` last used on this model (None before the first)."""
+        from ._decode_graph import current_session
+        return current_session(self)
+
+    # what a decode session (models/_decode_graph.py) asks of its model
+    def _session_weight(self):
+        return self.embed_tokens.weight
+
+    def _session_cache(self, batch, capacity, device):
+        return LlamaKVCache.allocate(self, batch, capacity, device)
+
+    def _session_logits(self, tok_cur, cache: LlamaKVCache):
+        return self._step_logits(tok_cur, cache, cache.capacity)
 
 
 def _make(**kw) -> LlamaForCausalLM:

@@ -193,3 +193,132 @@ def attention_extend(qkv_new: torch.Tensor, cache_k: torch.Tensor, cache_v: torc
         from . import _native_attn_extend
         return _native_attn_extend.attention_extend(qkv_new, cache_k, cache_v, lens, num_heads, max_len, new_lens)
     return attention_extend_reference(qkv_new, cache_k, cache_v, lens, num_heads, max_len, new_lens)
+
+
+# ------------------------------------------------------------------ grouped-query decode (rotated KV cache)
+# The Llama family's cache: cache_k / cache_v [B, Hkv, C, D] hold ROTATED keys for the Hkv key / value heads
+# (never expanded to the H query heads).  qkv_new [B, (H + 2 Hkv) D] is the new token's fused, UNROTATED
+# projection [q heads | k heads | v heads] and table the fp32 [n_pos, D] of ops.rope_table.  For row b with
+# n = lens[b] the query heads and the new key are rotated by table row n (HF half-split pairs, computed in
+# fp32 -- fp64 for fp64 inputs -- and rounded once to the input dtype: what ops.rope_qkv hands a full
+# forward); the G = H / Hkv query heads of KV head j attend to its cached keys 0..n-1 and to the new key, and
+# the rotated key and the value are stored to cache[b, :, n].  lens is NOT changed; max_len is the host's
+# upper bound on n + 1 and must fit both the cache and the table.
+def _gqa_heads(num_heads, num_kv_heads):
+    if num_kv_heads < 1 or num_heads < 1 or num_heads % num_kv_heads:
+        raise ValueError(f"num_heads {num_heads} must be a multiple of num_kv_heads {num_kv_heads}")
+
+
+def _check_gqa_cache(cache_k, cache_v, B, num_kv_heads, D):
+    if (cache_k.shape != cache_v.shape or cache_k.dim() != 4 or cache_k.shape[0] != B
+            or cache_k.shape[1] != num_kv_heads or cache_k.shape[3] != D):
+        raise ValueError(f"cache must be [B={B}, Hkv={num_kv_heads}, C, {D}] for keys and values, got "
+                         f"{tuple(cache_k.shape)} / {tuple(cache_v.shape)}")
+    if not (cache_k.is_contiguous() and cache_v.is_contiguous()):
+        raise ValueError("cache tensors must be contiguous")
+
+
+def _decode_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len):
+    if any(t.requires_grad for t in (qkv_new, table, cache_k, cache_v)):
+        raise RuntimeError("attention_decode_gqa has no autograd: call it under torch.no_grad() on detached tensors")
+    _gqa_heads(num_heads, num_kv_heads)
+    W = num_heads + 2 * num_kv_heads
+    if qkv_new.dim() != 2 or qkv_new.shape[1] % W or (qkv_new.shape[1] // W) % 2:
+        raise ValueError(f"qkv_new must be [B, (H + 2 Hkv)·D] with D even, got {tuple(qkv_new.shape)}")
+    B, D = qkv_new.shape[0], qkv_new.shape[1] // W
+    _check_gqa_cache(cache_k, cache_v, B, num_kv_heads, D)
+    if table.dim() != 2 or table.shape[1] != D:
+        raise ValueError(f"table must be [n_positions, {D}], got {tuple(table.shape)}")
+    if lens.dtype != torch.int32 or lens.shape != (B,) or not lens.is_contiguous():
+        raise ValueError("lens must be a contiguous int32 [B] tensor")
+    C = cache_k.shape[2]
+    if max_len > C:
+        raise ValueError(f"max_len {max_len} exceeds the cache capacity {C}")
+    if max_len < 1:
+        raise ValueError("max_len counts the new token: at least 1")
+    if max_len > table.shape[0]:
+        raise ValueError(f"max_len {max_len} exceeds the rotary table's {table.shape[0]} positions")
+    return D
+
+
+def attention_decode_gqa_reference(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: torch.Tensor,
+                                   cache_v: torch.Tensor, lens: torch.Tensor, num_heads: int, num_kv_heads: int,
+                                   max_len: int) -> torch.Tensor:
+    D = _decode_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len)
+    B, H, Hkv, half = qkv_new.shape[0], num_heads, num_kv_heads, D // 2
+    G = H // Hkv
+    dev = qkv_new.device
+    ct = torch.float64 if qkv_new.dtype == torch.float64 else torch.float32
+    n = lens.long()
+    x = qkv_new.to(ct).view(B, H + 2 * Hkv, D)
+    row = table[n].to(ct)                                                              # [B, D]
+    cos, sin = row[:, None, :half], row[:, None, half:]
+
+    def rot(t):
+        a, b = t[..., :half], t[..., half:]
+        return torch.cat([a * cos - b * sin, b * cos + a * sin], -1)
+
+    # rounded once to the input dtype: the operands a full forward sees after rope_qkv
+    q = rot(x[:, :H]).to(qkv_new.dtype)
+    k = rot(x[:, H:H + Hkv]).to(qkv_new.dtype)
+    v = qkv_new.view(B, H + 2 * Hkv, D)[:, H + Hkv:]
+    bi = torch.arange(B, device=dev)
+    cache_k[bi, :, n] = k.to(cache_k.dtype)
+    cache_v[bi, :, n] = v.to(cache_v.dtype)
+    live = torch.arange(max_len, device=dev).view(1, 1, 1, max_len) <= n.view(B, 1, 1, 1)
+    kk, vv = cache_k[:, :, :max_len].to(ct), cache_v[:, :, :max_len].to(ct)            # [B, Hkv, L, D]
+    s = q.to(ct).view(B, Hkv, G, D) @ kk.transpose(-1, -2) / math.sqrt(D)              # [B, Hkv, G, L]
+    # selects, not multiplies: a dead position may hold any bit pattern
+    p = torch.softmax(torch.where(live, s, torch.full_like(s, float("-inf"))), -1)
+    vv = torch.where(live.squeeze(1).unsqueeze(-1), vv, torch.zeros_like(vv))
+    return (p @ vv).reshape(B, H * D).to(qkv_new.dtype)
+
+
+def attention_decode_gqa(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
+                         lens: torch.Tensor, num_heads: int, num_kv_heads: int, max_len: int) -> torch.Tensor:
+    """Grouped-query single-query attention over the rotated cache, with the new token's rotation and the
+    append; returns ``[B, H·D]``."""
+    D = _decode_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len)
+    if (_lib.use_native(qkv_new, table, cache_k, cache_v, lens) and qkv_new.dtype == torch.bfloat16
+            and cache_k.dtype == torch.bfloat16 and cache_v.dtype == torch.bfloat16
+            and table.dtype == torch.float32 and D == 64):
+        from . import _native_attn_decode_gqa as N
+        if N.supported(num_heads, num_kv_heads):
+            return N.attention_decode_gqa(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len)
+    return attention_decode_gqa_reference(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len)
+
+
+def _fill_gqa_guard(packed, cache_k, cache_v, num_heads, num_kv_heads):
+    if any(t.requires_grad for t in (packed, cache_k, cache_v)):
+        raise RuntimeError("kv_cache_fill_gqa has no autograd: call it under torch.no_grad() on detached tensors")
+    _gqa_heads(num_heads, num_kv_heads)
+    if packed.dim() != 3 or packed.shape[2] % (3 * num_heads):
+        raise ValueError(f"packed must be rope_qkv's [B, S, 3·H·D], got {tuple(packed.shape)}")
+    D = packed.shape[2] // (3 * num_heads)
+    _check_gqa_cache(cache_k, cache_v, packed.shape[0], num_kv_heads, D)
+    if packed.shape[1] > cache_k.shape[2]:
+        raise ValueError(f"sequence length {packed.shape[1]} exceeds the cache capacity {cache_k.shape[2]}")
+    return D
+
+
+def kv_cache_fill_gqa_reference(packed: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor, num_heads: int,
+                                num_kv_heads: int) -> None:
+    D = _fill_gqa_guard(packed, cache_k, cache_v, num_heads, num_kv_heads)
+    B, S, _ = packed.shape
+    G = num_heads // num_kv_heads
+    _, k, v = packed.view(B, S, 3, num_heads, D)[:, :, :, ::G].permute(2, 0, 3, 1, 4).unbind(0)
+    cache_k[:, :, :S] = k.to(cache_k.dtype)
+    cache_v[:, :, :S] = v.to(cache_v.dtype)
+
+
+def kv_cache_fill_gqa(packed: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor, num_heads: int,
+                      num_kv_heads: int) -> None:
+    """After a prefill: from ``rope_qkv``'s packed ``[B, S, 3·H·D]`` (keys already rotated, every KV head
+    repeated to its G query-head slots) the first slot of every group goes to cache positions 0..S-1 of
+    ``[B, Hkv, C, D]`` (rows past a sequence's own length too: they are dead by ``lens``).  A bit copy."""
+    D = _fill_gqa_guard(packed, cache_k, cache_v, num_heads, num_kv_heads)
+    if (_lib.use_native(packed, cache_k, cache_v) and packed.dtype == torch.bfloat16
+            and cache_k.dtype == torch.bfloat16 and cache_v.dtype == torch.bfloat16 and D == 64):
+        from . import _native_attn_decode_gqa as N
+        return N.kv_cache_fill_gqa(packed, cache_k, cache_v, num_heads, num_kv_heads)
+    return kv_cache_fill_gqa_reference(packed, cache_k, cache_v, num_heads, num_kv_heads)
