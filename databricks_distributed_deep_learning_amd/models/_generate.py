@@ -1,7 +1,7 @@
 """What the causal LMs' ``generate`` share: the argument checks, the prompt compaction and the two token loops.
 
 A model's ``generate`` checks its own position limit, compacts the prompts, switches to eval, consumes the
-prompt into a cache (its own business: ``prefill``, or GPT-2's ``extend`` paths) and hands the resulting
+prompt into a cache (its own business: ``prefill``, or the ``extend`` paths) and hands the resulting
 next-token logits to ``token_loop`` (one ``decode_step`` per token, sampling in plain torch) or
 ``session_loop`` (the step of a decode session, ``models/_decode_graph.py``).
 """

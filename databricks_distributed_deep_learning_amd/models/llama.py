@@ -23,8 +23,13 @@ token's queries and key by the row's own position, scores every cached row once 
 its group and appends.  ``generate(use_graph=True)`` runs the step from a decode session
 (``models/_decode_graph.py``): captured once into a hipGraph and replayed per token.
 
-Not covered: ``extend`` (``prefix=`` / ``prefill_chunk=``) for this family, ``rope_scaling``, sliding-window
-attention, biased projections.
+``extend`` adds a chunk of T tokens per sequence to a cache that already holds something
+(``ops.attention_extend_gqa``: the chunk is rotated by each row's own positions inside the attention kernel --
+there is no position embedding to add); ``generate(prefix=...)`` starts from a copy of a prefilled cache and
+``prefill(chunk=...)`` consumes a prompt through ``extend`` in chunks.
+
+Not covered: ``generate(prefill_chunk=...)`` (chunked prompt consumption is on ``prefill``), ``rope_scaling``,
+sliding-window attention, biased projections.
 """
 from __future__ import annotations
 
@@ -97,6 +102,29 @@ class LlamaKVCache:
     def v(self, layer: int) -> torch.Tensor:
         return self.data[layer, 1]
 
+    def copy_prefix_(self, src: "LlamaKVCache") -> "LlamaKVCache":
+        """Start this cache from ``src``'s contents: positions ``< src.max_len`` of every layer, ``lens`` and
+        ``max_len``.  ``src`` has this cache's batch or batch 1 (one prefix shared by every row), its dtype and
+        its device (nothing is converted or moved silently); it is only read.  Rows of ``src`` may have unequal
+        ``lens``: ``src.max_len``, their bound, is what is copied and what ``generate`` counts against
+        ``max_position_embeddings``."""
+        L, _, B, H, C, D = self.data.shape
+        Ls, _, Bs, Hs, _, Ds = src.data.shape
+        if (Ls, Hs, Ds) != (L, H, D):
+            raise ValueError(f"prefix cache has {Ls} layers of {Hs} KV heads x {Ds}, this one {L} of {H} x {D}")
+        if Bs not in (1, B):
+            raise ValueError(f"prefix cache batch {Bs} must be 1 or {B}")
+        if src.data.dtype != self.data.dtype or src.data.device != self.data.device:
+            raise ValueError(f"prefix cache is {src.data.dtype} on {src.data.device}, this one {self.data.dtype} on "
+                             f"{self.data.device}")
+        if src.max_len > C:
+            raise ValueError(f"prefix length {src.max_len} exceeds the cache capacity {C}")
+        n = src.max_len
+        self.data[:, :, :, :, :n].copy_(src.data[:, :, :, :, :n])
+        self.lens.copy_(src.lens)
+        self.max_len = n
+        return self
+
 
 class LlamaBlock(nn.Module):
     def __init__(self, c: LlamaConfig):
@@ -137,9 +165,30 @@ class LlamaBlock(nn.Module):
         qkv = lin(self.input_layernorm(h_new), self.qkv.weight, None)
         ctx = ops.attention_decode_gqa(qkv, table, cache.k(layer), cache.v(layer), cache.lens, self.num_heads,
                                        self.num_kv_heads, cache.max_len + 1 if len_bound is None else len_bound)
-        h = lin(ctx, self.o_proj.weight, None, residual=h_new)
+        return self._small_m_tail(ctx, h_new)
+
+    def _small_m_tail(self, ctx, h):
+        """Output projection and MLP of a block on M <= 16 rows (``ops.linear_small_m``)."""
+        lin = ops.linear_small_m
+        h = lin(ctx, self.o_proj.weight, None, residual=h)
         z = ops.swiglu(lin(self.post_attention_layernorm(h), self.gate_up.weight, None))
         return lin(z, self.down_proj.weight, None, residual=h)
+
+    def extend(self, h, table, cache: LlamaKVCache, layer: int, new_lens=None, len_bound=None):
+        """A chunk of new tokens per sequence, ``h [B, T, E]``, against the cache, which gains the rotated keys
+        and the values of each row's first ``new_lens`` (default T) tokens: ``prefill`` with
+        ``ops.attention_extend_gqa`` in place of rope + attention + fill.  ``len_bound``: the bound on ``lens``
+        (default ``max_len``).  With ``B T <= 16`` the linears are the weight-streaming ones of ``decode``."""
+        small = h.shape[0] * h.shape[1] <= 16
+        y = self.input_layernorm(h)
+        qkv = ops.linear_small_m(y, self.qkv.weight, None) if small else self.qkv(y)
+        ctx = ops.attention_extend_gqa(qkv, table, cache.k(layer), cache.v(layer), cache.lens, self.num_heads,
+                                       self.num_kv_heads, cache.max_len if len_bound is None else len_bound,
+                                       new_lens)
+        if small:
+            return self._small_m_tail(ctx, h)
+        h = self.o_proj(ctx, residual=h)
+        return self.down_proj(ops.swiglu(self.gate_up(self.post_attention_layernorm(h))), residual=h)
 
 
 class LlamaForCausalLM(nn.Module):
@@ -203,13 +252,26 @@ class LlamaForCausalLM(nn.Module):
         return ops.linear(h, w, None)
 
     # ------------------------------------------------------------ generation
-    def prefill(self, input_ids, lens, cache: LlamaKVCache):
+    def prefill(self, input_ids, lens, cache: LlamaKVCache, chunk: int = None):
         """Right-padded prompts ``[B, S]`` of lengths ``lens`` (int ``[B]``, on the device) -> the next-token
         logits ``[B, vocab]`` of each sequence's last token; fills ``cache`` and sets its lengths.  The head
-        runs on those B rows only: the ``[B, S, vocab]`` logits never exist."""
+        runs on those B rows only: the ``[B, S, vocab]`` logits never exist.
+
+        ``chunk``: the prompt is consumed from an empty cache through ``extend`` in chunks of that many
+        columns, which bounds the prompt's activations by the chunk.  A row whose prompt ended before a chunk
+        passes ``new_lens = 0`` there and keeps the logits of the chunk that held its last token;
+        ``cache.max_len`` ends at S either way."""
         B, S = input_ids.shape
         if S > cache.capacity:
             raise ValueError(f"prompt length {S} exceeds the cache capacity {cache.capacity}")
+        if chunk is not None:
+            if chunk < 1:
+                raise ValueError("chunk must be at least 1")
+            with torch.no_grad():
+                cache.lens.zero_()
+                cache.max_len = 0
+                return self._extend_chunks(input_ids, lens.to(device=input_ids.device, dtype=torch.int32), cache,
+                                           chunk)
         with torch.no_grad():
             lens = lens.to(device=input_ids.device, dtype=torch.int32)
             keep = torch.arange(S, device=input_ids.device)[None, :] < lens[:, None]
@@ -221,6 +283,61 @@ class LlamaForCausalLM(nn.Module):
             cache.lens.copy_(lens)
             cache.max_len = S
             return ops.linear_small_m(self.norm(last), self.head_weight(), None)
+
+    def extend(self, input_ids, cache: LlamaKVCache, new_lens=None, all_logits: bool = False):
+        """``input_ids [B, T]``: the tokens at positions ``cache.lens + 0 .. T-1`` of each sequence, right-padded
+        to T, of which row b's first ``new_lens[b]`` are real (int ``[B]`` on the device; default T) -> the
+        next-token logits ``[B, vocab]`` at each row's last new token (the head runs on those B rows only), or
+        with ``all_logits`` the ``[B, T, vocab]`` logits of every column (padded ones are meaningless).  Every
+        layer appends the real tokens' rotated keys and their values; then ``cache.lens += new_lens`` and
+        ``cache.max_len += T``.  From an empty cache this is ``prefill``.  Positions enter only through the
+        rotary table rows the attention kernel reads (``lens[b] + i``, on the device).
+
+        ``new_lens[b] == 0`` is allowed: the row is handed one dead column (the attention wants at least one
+        query per row), whose key / value land at position ``lens[b]`` -- which stays dead, since the row's
+        length does not advance, and is overwritten by the row's next real token.  Its logits are meaningless."""
+        B, T = input_ids.shape
+        if T < 1:
+            raise ValueError("extend needs at least one column")
+        if cache.max_len + T > cache.capacity:
+            raise ValueError(f"max_len {cache.max_len} + {T} new columns exceeds the cache capacity {cache.capacity}")
+        with torch.no_grad():
+            dev = input_ids.device
+            adv = q_lens = None
+            if new_lens is not None:
+                adv = new_lens.to(device=dev, dtype=torch.int32).clamp(0, T)
+                q_lens = adv.clamp(min=1)
+            h = self.embed_tokens(input_ids)
+            for i, blk in enumerate(self.layers):
+                h = blk.extend(h, self.rope_table, cache, i, q_lens)
+            if all_logits:
+                logits = ops.linear(self.norm(h), self.head_weight(), None)
+            else:
+                last = h[:, -1] if q_lens is None else h[torch.arange(B, device=dev), (q_lens - 1).long()]
+                logits = ops.linear_small_m(self.norm(last), self.head_weight(), None)
+            cache.lens += T if adv is None else adv
+            cache.max_len += T
+            return logits
+
+    def _extend_chunks(self, ids, cnt, cache: LlamaKVCache, step: int):
+        """The right-padded prompts ``ids [B, S0]`` of lengths ``cnt`` on top of what ``cache`` holds, through
+        ``extend`` in chunks of ``step`` columns -> each row's next-token logits (those of the chunk that held
+        its last token; a row whose prompt ended before a chunk passes ``new_lens = 0`` there)."""
+        S0 = ids.shape[1]
+        logits = None
+        for c0 in range(0, S0, step):
+            T = min(step, S0 - c0)
+            new = self.extend(ids[:, c0:c0 + T], cache, (cnt - c0).clamp(0, T))
+            logits = new if logits is None else torch.where((cnt > c0)[:, None], new, logits)
+        return logits
+
+    def _consume_prompt(self, ids, cnt, cache: LlamaKVCache, prefix=None):
+        """The right-padded prompts into ``cache`` -> each row's next-token logits: ``prefill``, or with
+        ``prefix`` a copy of it extended by the whole prompt."""
+        if prefix is None:
+            return self.prefill(ids, cnt, cache)
+        cache.copy_prefix_(prefix)
+        return self._extend_chunks(ids, cnt, cache, ids.shape[1])
 
     def decode_step(self, tokens, cache: LlamaKVCache, len_bound=None):
         """``tokens [B]``: the token at position ``cache.lens`` of each sequence -> the next-token logits
@@ -248,7 +365,7 @@ class LlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, max_new_tokens: int = 20, do_sample: bool = False,
                  temperature: float = 1.0, top_k=None, eos_token_id=None, pad_token_id=None, generator=None,
-                 use_graph: bool = False):
+                 use_graph: bool = False, prefix: LlamaKVCache = None):
         """Greedy (argmax) or sampled (temperature, then top-k, then multinomial) continuation of
         ``input_ids [B, S_in]`` -> ``[B, S_in + n_new]``: ``GPT2LMHeadModel.generate``'s contract.  Each row
         as given, then its generated tokens, with ``pad_token_id`` (default ``eos_token_id``) after the first
@@ -265,31 +382,39 @@ class LlamaForCausalLM(nn.Module):
         parameter's storage changes).  Elsewhere the same loop runs eagerly.  Greedy output equals
         ``use_graph=False``'s; with ``do_sample`` the tokens follow ``ops.next_token``'s definition from one
         ``torch.rand(max_new_tokens, B, generator=generator)`` drawn before the loop.  The eos check syncs
-        only every 16 steps; the result is trimmed to the length ``use_graph=False`` returns."""
+        only every 16 steps; the result is trimmed to the length ``use_graph=False`` returns.
+
+        ``prefix``: a ``LlamaKVCache`` (of batch B, or of batch 1 and shared by every row) that already holds
+        the tokens before ``input_ids``, e.g. a system prompt prefilled once: it is copied into this call's
+        own cache (the session's, under ``use_graph``), never modified, and the prompt is consumed by
+        ``extend`` on top of it, so row b's prompt starts at rotary position ``prefix.lens[b]``."""
         B, S_in = input_ids.shape
         G.check_sampling(max_new_tokens, do_sample, temperature, top_k)
         n_pos = self.config.max_position_embeddings
-        if S_in + max_new_tokens > n_pos:
-            raise ValueError(f"S_in + max_new_tokens = {S_in + max_new_tokens} exceeds max_position_embeddings "
-                             f"{n_pos}")
+        P0 = 0 if prefix is None else prefix.max_len
+        if P0 + S_in + max_new_tokens > n_pos:
+            raise ValueError(f"{'prefix + ' if prefix is not None else ''}S_in + max_new_tokens = "
+                             f"{P0 + S_in + max_new_tokens} exceeds max_position_embeddings {n_pos}")
         dev = input_ids.device
         ids, cnt, S0 = G.compact_prompts(input_ids, attention_mask)
         if pad_token_id is None:
             pad_token_id = eos_token_id
+        need = P0 + S0 + max_new_tokens
         was_training = self.training
         self.eval()
         try:
             if use_graph:
                 from ._decode_graph import round_capacity, session_for
-                sess = session_for(self, B, round_capacity(S0 + max_new_tokens, n_pos),
+                sess = session_for(self, B, round_capacity(need, n_pos),
                                    G.use_graph_for(self.embed_tokens.weight))
-                new = G.session_loop(sess, lambda cache: self.prefill(ids, cnt, cache), B, dev, max_new_tokens,
-                                     do_sample, temperature, top_k, eos_token_id, pad_token_id, generator)
+                new = G.session_loop(sess, lambda cache: self._consume_prompt(ids, cnt, cache, prefix), B, dev,
+                                     max_new_tokens, do_sample, temperature, top_k, eos_token_id, pad_token_id,
+                                     generator)
             else:
-                cache = LlamaKVCache.allocate(self, B, S0 + max_new_tokens, dev)
-                new = G.token_loop(self.prefill(ids, cnt, cache), lambda tok: self.decode_step(tok, cache),
-                                   max_new_tokens, do_sample, temperature, top_k, eos_token_id, pad_token_id,
-                                   generator)
+                cache = LlamaKVCache.allocate(self, B, need, dev)
+                new = G.token_loop(self._consume_prompt(ids, cnt, cache, prefix),
+                                   lambda tok: self.decode_step(tok, cache), max_new_tokens, do_sample,
+                                   temperature, top_k, eos_token_id, pad_token_id, generator)
         finally:
             self.train(was_training)
         return torch.cat([input_ids, new.to(input_ids.dtype)], 1)

@@ -322,3 +322,103 @@ def kv_cache_fill_gqa(packed: torch.Tensor, cache_k: torch.Tensor, cache_v: torc
         from . import _native_attn_decode_gqa as N
         return N.kv_cache_fill_gqa(packed, cache_k, cache_v, num_heads, num_kv_heads)
     return kv_cache_fill_gqa_reference(packed, cache_k, cache_v, num_heads, num_kv_heads)
+
+
+# ------------------------------------------------------------------ grouped-query extend (rotated KV cache)
+# A chunk of T new tokens per sequence against the Llama family's cache.  qkv_new [B, T, (H + 2 Hkv) D] is the
+# chunk's fused, UNROTATED projection and table the fp32 [n_pos, D] of ops.rope_table.  For row b with
+# n = lens[b] (clamped to 0 .. max_len) and t = new_lens[b] (clamped to 1 .. T; T without new_lens: rows are
+# right-padded), chunk token i < t has its H query heads and Hkv key heads rotated by table row n + i (HF
+# half-split pairs, computed in fp32 -- fp64 for fp64 inputs -- and rounded once to the input dtype: what
+# ops.rope_qkv hands a full forward).  Query i of head h attends to cached keys 0..n-1 of KV head h / G and to
+# the rotated chunk keys 0..i of that head; output rows i >= t are zeros.  The rotated key and the value of
+# chunk positions i < t are stored to cache[b, :, n+i]; nothing else in the cache changes.  (A caller that must
+# pass a row with no real token hands it t = 1, as for attention_extend.)  lens and new_lens are NOT changed;
+# max_len is the host's upper bound on lens, and max_len + T must fit both the cache and the table.
+def _extend_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len, new_lens):
+    if any(t.requires_grad for t in (qkv_new, table, cache_k, cache_v)):
+        raise RuntimeError("attention_extend_gqa has no autograd: call it under torch.no_grad() on detached tensors")
+    _gqa_heads(num_heads, num_kv_heads)
+    W = num_heads + 2 * num_kv_heads
+    if qkv_new.dim() != 3 or qkv_new.shape[1] < 1 or qkv_new.shape[2] % W or (qkv_new.shape[2] // W) % 2:
+        raise ValueError(f"qkv_new must be [B, T >= 1, (H + 2 Hkv)·D] with D even, got {tuple(qkv_new.shape)}")
+    B, T, D = qkv_new.shape[0], qkv_new.shape[1], qkv_new.shape[2] // W
+    _check_gqa_cache(cache_k, cache_v, B, num_kv_heads, D)
+    if table.dim() != 2 or table.shape[1] != D:
+        raise ValueError(f"table must be [n_positions, {D}], got {tuple(table.shape)}")
+    for name, t in (("lens", lens), ("new_lens", new_lens)):
+        if t is not None and (t.dtype != torch.int32 or t.shape != (B,) or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous int32 [B] tensor")
+    C = cache_k.shape[2]
+    if max_len < 0:
+        raise ValueError("max_len bounds lens: at least 0")
+    if max_len + T > C:
+        raise ValueError(f"max_len {max_len} + the chunk's {T} tokens exceeds the cache capacity {C}")
+    if max_len + T > table.shape[0]:
+        raise ValueError(f"max_len {max_len} + the chunk's {T} tokens exceeds the rotary table's {table.shape[0]} "
+                         f"positions")
+    return D
+
+
+def attention_extend_gqa_reference(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: torch.Tensor,
+                                   cache_v: torch.Tensor, lens: torch.Tensor, num_heads: int, num_kv_heads: int,
+                                   max_len: int, new_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    D = _extend_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len, new_lens)
+    B, T, _ = qkv_new.shape
+    H, Hkv, half = num_heads, num_kv_heads, D // 2
+    G = H // Hkv
+    dev = qkv_new.device
+    ct = torch.float64 if qkv_new.dtype == torch.float64 else torch.float32
+    n = lens.long().clamp(0, max_len)
+    t = torch.full_like(n, T) if new_lens is None else new_lens.long().clamp(1, T)
+    i = torch.arange(T, device=dev)
+    qlive = i.view(1, T) < t.view(B, 1)                                                # [B, T]
+    # a padded column rotates by its row's last real position (its result is dropped: the table stays in bounds)
+    pos = n.view(B, 1) + torch.minimum(i.view(1, T), t.view(B, 1) - 1)
+    x = qkv_new.view(B, T, H + 2 * Hkv, D)
+    row = table[pos].to(ct)                                                            # [B, T, D]
+    cos, sin = row[:, :, None, :half], row[:, :, None, half:]
+
+    def rot(u):
+        a, b = u[..., :half], u[..., half:]
+        return torch.cat([a * cos - b * sin, b * cos + a * sin], -1)
+
+    # rounded once to the input dtype: the operands a full forward sees after rope_qkv
+    q = rot(x[:, :, :H].to(ct)).to(qkv_new.dtype).permute(0, 2, 1, 3)                   # [B, H, T, D]
+    k = rot(x[:, :, H:H + Hkv].to(ct)).to(qkv_new.dtype).permute(0, 2, 1, 3)            # [B, Hkv, T, D]
+    v = x[:, :, H + Hkv:].permute(0, 2, 1, 3)
+    # keys: the cache's first max_len positions (live while < n), then the chunk (live while <= the query)
+    clive = torch.arange(max_len, device=dev).view(1, max_len) < n.view(B, 1)          # [B, L]
+    live = torch.cat([clive.view(B, 1, max_len).expand(B, T, max_len),
+                      (i.view(1, 1, T) <= i.view(1, T, 1)).expand(B, T, T)], 2).view(B, 1, 1, T, max_len + T)
+    kk = torch.cat([cache_k[:, :, :max_len].to(ct), k.to(ct)], 2)                      # [B, Hkv, L + T, D]
+    vv = torch.cat([cache_v[:, :, :max_len].to(ct), v.to(ct)], 2)
+    s = q.to(ct).reshape(B, Hkv, G, T, D) @ kk.unsqueeze(2).transpose(-1, -2) / math.sqrt(D)
+    # selects, not multiplies: a dead position (and a padded chunk row) may hold any bit pattern
+    p = torch.softmax(torch.where(live, s, torch.full_like(s, float("-inf"))), -1)
+    vlive = torch.cat([clive, qlive], 1)                                               # [B, L + T]
+    vv = torch.where(vlive.view(B, 1, -1, 1), vv, torch.zeros_like(vv))
+    o = torch.where(qlive.view(B, 1, 1, T, 1), p @ vv.unsqueeze(2), torch.zeros((), dtype=ct, device=dev))
+    # the append: chunk position i < t of row b to cache position n + i
+    bi, ii = torch.nonzero(qlive, as_tuple=True)
+    cache_k[bi, :, n[bi] + ii] = k.to(cache_k.dtype)[bi, :, ii]
+    cache_v[bi, :, n[bi] + ii] = v.to(cache_v.dtype)[bi, :, ii]
+    return o.reshape(B, H, T, D).permute(0, 2, 1, 3).reshape(B, T, H * D).to(qkv_new.dtype)
+
+
+def attention_extend_gqa(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
+                         lens: torch.Tensor, num_heads: int, num_kv_heads: int, max_len: int,
+                         new_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Grouped-query causal attention of a chunk of new tokens over the rotated cache plus the chunk, with the
+    chunk's rotation and the append; returns ``[B, T, H·D]``."""
+    D = _extend_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len, new_lens)
+    if (_lib.use_native(qkv_new, table, cache_k, cache_v, lens, new_lens) and qkv_new.dtype == torch.bfloat16
+            and cache_k.dtype == torch.bfloat16 and cache_v.dtype == torch.bfloat16
+            and table.dtype == torch.float32 and D == 64):
+        from . import _native_attn_decode_gqa as N
+        if N.supported(num_heads, num_kv_heads):
+            from . import _native_attn_extend_gqa
+            return _native_attn_extend_gqa.attention_extend_gqa(qkv_new, table, cache_k, cache_v, lens, num_heads,
+                                                                num_kv_heads, max_len, new_lens)
+    return attention_extend_gqa_reference(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len,
+                                          new_lens)
