@@ -213,10 +213,19 @@ __device__ __forceinline__ bf16x8 load_frag_global(const bf16_t* rowp, int kk) {
 // last query (nt is per workgroup), the workgroups run from the last query tile -- the longest
 // loop -- to the first (tile on grid y), and only tiles the diagonal cuts for this wave's 16 rows pay the per-score
 // compare; a tile wholly above it gives exp2(-inf) = 0 for every score
-template <bool MASK, bool DROP, bool CAUSAL = false>
+// DOC (with CAUSAL): packed rows -- query i sees keys doc_start[b, i] <= j <= i, doc_start the row index of
+// the first token of i's document (non-decreasing along a row).  The key-tile loop STARTS at the tile
+// that holds the doc_start of the workgroup's first query, the smallest of its rows; each lane keeps its
+// own row's bound in a register, loaded once up here (never inside the loop: see s_mk), and only tiles
+// that the document start of one of this wave's 16 rows cuts pay the second compare, as `diag` gates
+// the first.  With doc_start all zero the tile sequence and every instruction's operands are those of
+// the plain causal instance.
+template <bool MASK, bool DROP, bool CAUSAL = false, bool DOC = false>
 __global__ __launch_bounds__(64 * TWF, 1) void attn_fwd_k(const bf16_t* __restrict__ qkv, const float* __restrict__ mask,
                                                   bf16_t* __restrict__ out, float* __restrict__ lse, int B, int S, int H,
-                                                  float scale, float p_drop, uint64_t seed, uint32_t* __restrict__ dmask) {
+                                                  float scale, float p_drop, uint64_t seed, uint32_t* __restrict__ dmask,
+                                                  const int* __restrict__ doc_start = nullptr) {
+    static_assert(!DOC || (CAUSAL && !MASK), "DOC: on top of the causal compare, no key-bias instance");
     __shared__ __attribute__((aligned(16))) char smem[4 * TK * ROWB];   // K0 V0 K1 V1
     // the tiles' additive key mask (scaled to log2), staged with K / V: an in-loop global load of
     // it made the compiler wait out the K / V prefetch (vmcnt counts every load in order)
@@ -259,6 +268,18 @@ __global__ __launch_bounds__(64 * TWF, 1) void attn_fwd_k(const bf16_t* __restri
     float mL = 0.f;                                          // CAUSAL: fl(m * log2e), 0 while m = -inf
     // causal: up to the tile of the workgroup's last query (2 qt + 2 tiles: whole 128-key keep words)
     const int nt = CAUSAL ? min(qt * TROWS_F + TROWS_F - 1, S - 1) / TK + 1 : (S + TK - 1) / TK;
+    // DOC: my row's first visible key; the wave's largest (the tiles below it are cut for some row); the
+    // workgroup's first tile, clamped into the loop's range whatever the tensor holds
+    int myds = 0, wds = 0, t0 = 0;
+    if (DOC) {
+        const int* dsrow = doc_start + (long)b * S;
+        myds = qok ? dsrow[myq] : 0;
+        wds = myds;
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) wds = max(wds, __shfl_xor(wds, o, 64));
+        wds = __builtin_amdgcn_readfirstlane(wds);
+        t0 = min(max(dsrow[qt * TROWS_F] / TK, 0), nt - 1);
+    }
     uint32_t kbits = 0;                                      // dropout keep bits of a 128-key word
     Stager<64 * TWF> sk, sv;
     float nmk = 0.f;                                         // raw load; scaled / bounded at the store
@@ -268,14 +289,14 @@ __global__ __launch_bounds__(64 * TWF, 1) void attn_fwd_k(const bf16_t* __restri
         mk_ok = k < S;
         if (MASK && threadIdx.x < TK) nmk = mrow[min(k, S - 1)];
     };
-    sk.load(kb, rs, 0, S);
-    sv.load(vb, rs, 0, S);
-    load_mk(0);
-    sk.store<false>(smem);
-    sv.store<true>(smem + TK * ROWB);
-    if (MASK && threadIdx.x < TK) s_mk[0][threadIdx.x] = mk_ok ? nmk * mks : 0.f;
+    sk.load(kb, rs, t0 * TK, S);
+    sv.load(vb, rs, t0 * TK, S);
+    load_mk(t0);
+    sk.store<false>(smem + (t0 & 1) * 2 * TK * ROWB);
+    sv.store<true>(smem + (t0 & 1) * 2 * TK * ROWB + TK * ROWB);
+    if (MASK && threadIdx.x < TK) s_mk[t0 & 1][threadIdx.x] = mk_ok ? nmk * mks : 0.f;
     __syncthreads();
-    for (int t = 0; t < nt; ++t) {
+    for (int t = t0; t < nt; ++t) {
         char* sK = smem + (t & 1) * 2 * TK * ROWB;
         char* sV = sK + TK * ROWB;
         const float* sM = s_mk[t & 1];
@@ -299,6 +320,7 @@ __global__ __launch_bounds__(64 * TWF, 1) void attn_fwd_k(const bf16_t* __restri
         float tmax = -INFINITY;
         const bool tail = (t + 1) * TK > S;          // uniform: keys past S in this tile
         const bool diag = CAUSAL && t * TK + TK - 1 > q0;   // per wave: keys past its first query
+        const bool cut = DOC && t * TK < wds;               // per wave: keys before a row's document
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk) {
             const int k0 = t * TK + 16 * blk + 4 * g;
@@ -311,6 +333,7 @@ __global__ __launch_bounds__(64 * TWF, 1) void attn_fwd_k(const bf16_t* __restri
                 if (MASK) v += mk[r];
                 if (tail && k0 + r >= S) v = -INFINITY;
                 if (CAUSAL && diag && k0 + r > myq) v = -INFINITY;
+                if (DOC && cut && k0 + r < myds) v = -INFINITY;
                 s[blk][r] = v;
                 tmax = fmaxf(tmax, v);
             }
@@ -413,13 +436,21 @@ __global__ __launch_bounds__(256) void attn_delta_k(const bf16_t* __restrict__ d
 // which more resident waves hide (same for the dQ kernel below)
 // CAUSAL: the query-tile loop starts at the diagonal tile (the workgroup's own 64 positions); the
 // first workgroups have the longest loops
-template <bool DROP, bool CAUSAL = false>
+// DOC (with CAUSAL): key j is seen by queries j <= i < doc_end[b, j], the exclusive end of j's document
+// (the same pairs as doc_start[b, i] <= j).  The query-tile loop ENDS at the tile that holds
+// doc_end - 1 of the workgroup's last live key, the largest of its rows.  Each lane keeps its key's
+// bound in a register, min(doc_end, S) (0 for a key past S), and the compare against it REPLACES the
+// `q < S && kok` compare of the other instances: no tile pays anything new, and no per-wave gate with its
+// own registers is needed (with one the DROP instance spilled a 64-bit address that it reloaded per tile)
+template <bool DROP, bool CAUSAL = false, bool DOC = false>
 __global__ __launch_bounds__(64 * TWB, 3) void attn_bwd_dkv_k(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                       const float* __restrict__ lse, const float* __restrict__ delta,
                                                       const float* __restrict__ mask, bf16_t* __restrict__ dqkv, int B,
                                                       int S, int H, float scale, float p_drop,
                                                       const uint32_t* __restrict__ dmask,
-                                                      float* __restrict__ colsum) {
+                                                      float* __restrict__ colsum,
+                                                      const int* __restrict__ doc_end = nullptr) {
+    static_assert(!DOC || CAUSAL, "DOC: on top of the causal compare");
     // Q, dO tiles as ONE image each on the transposed-read swizzle, read both as rows (S, dP
     // fragments) and transposed (dK, dV fragments) without bank conflicts (the row swizzle had
     // 23 % conflicted tr reads; a second, transposed copy of each tile doubled the staging)
@@ -449,6 +480,8 @@ __global__ __launch_bounds__(64 * TWB, 3) void attn_bwd_dkv_k(const bf16_t* __re
         kf[0] = load_frag_global(kr, 0); kf[1] = load_frag_global(kr, 1);
         vf[0] = load_frag_global(vr, 0); vf[1] = load_frag_global(vr, 1);
     }
+    // (kept a run-time value in the DOC instances too, whose mask is null: as a constant 0 the compiler
+    // contracts the exponent differently, and all-zero doc_start is no longer the causal call bit for bit)
     const float mbias = (mask && kok) ? mask[(long)b * S + myk] : 0.f;
     const float c2 = scale * LOG2E;
     const float inv_keep = DROP ? 1.f / (1.f - p_drop) : 1.f;
@@ -464,7 +497,17 @@ __global__ __launch_bounds__(64 * TWB, 3) void attn_bwd_dkv_k(const bf16_t* __re
     for (int i = 0; i < 4; ++i) { dv[i] = (f32x4){0, 0, 0, 0}; dk[i] = (f32x4){0, 0, 0, 0}; }
     char* sQ = smem;
     char* sO = smem + TQ * ROWB;
-    const int nt = (S + TQ - 1) / TQ;
+    const int t0 = CAUSAL ? (int)kt : 0;   // causal: queries before the keys' tile see none of them
+    int nt = (S + TQ - 1) / TQ;
+    int qlim = S;                          // DOC: the first query that no longer sees my key
+    if (DOC) {
+        const int* derow = doc_end + (long)b * S;
+        qlim = kok ? min(derow[myk], S) : 0;
+        // one past the tile of the last query that sees a key of this workgroup, clamped into the
+        // loop's range whatever the tensor holds
+        const int kl = min((int)kt * TROWS_B + TROWS_B - 1, S - 1);
+        nt = min(max((derow[kl] - 1) / TQ + 1, t0 + 1), nt);
+    }
     // tile t+1's Q / dO rows, keep words, LSE and delta are loaded into registers while tile t
     // computes (the single-buffered loop waited out every tile's loads)
     Stager<64 * TWB> a, c;
@@ -481,7 +524,6 @@ __global__ __launch_bounds__(64 * TWB, 3) void attn_bwd_dkv_k(const bf16_t* __re
             ndel = q < S ? delta[(long)bh * S + q] : 0.f;
         }
     };
-    const int t0 = CAUSAL ? (int)kt : 0;   // causal: queries before the keys' tile see none of them
     fetch(t0);
     for (int t = t0; t < nt; ++t) {
         __syncthreads();             // previous tile fully consumed
@@ -516,7 +558,7 @@ __global__ __launch_bounds__(64 * TWB, 3) void attn_bwd_dkv_k(const bf16_t* __re
             for (int r = 0; r < 4; ++r) {
                 const int ql = 16 * qbk + 4 * g + r;
                 const int q = t * TQ + ql;
-                bool ok = q < S && kok;
+                bool ok = DOC ? q < qlim : q < S && kok;
                 if (CAUSAL && t == t0 && myk > q) ok = false;   // the diagonal tile
                 float pv = ok ? fast_exp2(sc[qbk][r] * c2 + mbias * LOG2E - s_lse[ql] * LOG2E) : 0.f;
                 float dpv = dp[qbk][r];
@@ -578,13 +620,19 @@ __global__ __launch_bounds__(64 * TWB, 3) void attn_bwd_dkv_k(const bf16_t* __re
 // workgroup = 16 TWB queries; wave owns 16 queries (query on the lane), loops over key tiles.
 // CAUSAL: the key-tile loop ends at the diagonal tile; the workgroups run from the last query tile
 // (the longest loop) to the first
-template <bool MASK, bool DROP, bool CAUSAL = false>
+// DOC (with CAUSAL): as in the forward -- the key-tile loop starts at the tile of the doc_start of the
+// workgroup's first query, each lane holds its row's doc_start, and only tiles cut by the document start
+// of one of this wave's 16 rows pay the compare.  Its 64 rows are half of a forward workgroup's 128, so
+// it visits no tile (and uses no keep word) that the forward skipped
+template <bool MASK, bool DROP, bool CAUSAL = false, bool DOC = false>
 __global__ __launch_bounds__(64 * TWB, 3) void attn_bwd_dq_k(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                      const float* __restrict__ lse, const float* __restrict__ delta,
                                                      const float* __restrict__ mask, bf16_t* __restrict__ dqkv, int B,
                                                      int S, int H, float scale, float p_drop,
                                                      const uint32_t* __restrict__ dmask,
-                                                     float* __restrict__ colsum) {
+                                                     float* __restrict__ colsum,
+                                                     const int* __restrict__ doc_start = nullptr) {
+    static_assert(!DOC || (CAUSAL && !MASK), "DOC: on top of the causal compare, no key-bias instance");
     __shared__ __attribute__((aligned(16))) char smem[2 * TK * ROWB];   // K (tr swizzle: read both ways), V tiles
     __shared__ __attribute__((aligned(16))) float s_mk[TK];            // the tile's additive key mask (log2)
     const int bh = CAUSAL ? blockIdx.x : blockIdx.y, b = bh / H, h = bh - b * H;   // causal grid as in the dKV kernel
@@ -611,13 +659,26 @@ __global__ __launch_bounds__(64 * TWB, 3) void attn_bwd_dq_k(const bf16_t* __res
     const float c2 = scale * LOG2E;
     const float inv_keep = DROP ? 1.f / (1.f - p_drop) : 1.f;
     const float* mrow = MASK ? mask + (long)b * S : nullptr;
+    static_assert(TROWS_B == TK, "causal: a workgroup's queries are one key tile, the diagonal one");
+    const int nt = CAUSAL ? qt + 1 : (S + TK - 1) / TK;
+    int myds = 0, wds = 0, t0 = 0;       // DOC: as in the forward
+    if (DOC) {
+        const int* dsrow = doc_start + (long)b * S;
+        myds = qok ? dsrow[myq] : 0;
+        wds = myds;
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) wds = max(wds, __shfl_xor(wds, o, 64));
+        wds = __builtin_amdgcn_readfirstlane(wds);
+        t0 = min(max(dsrow[min(qt * TROWS_B, S - 1)] / TK, 0), nt - 1);
+    }
     // this query's keep words, one per 128 keys, loaded up front (S <= 512 here: 4 words)
     constexpr int MAXKW = 4;
     uint32_t kwds[MAXKW] = {~0u, ~0u, ~0u, ~0u};
     if (DROP && qok) {
 #pragma unroll
         for (int i = 0; i < MAXKW; ++i)
-            if (i < dmask_nkw(S) && !(CAUSAL && i > (qt >> 1)))   // causal: words past the diagonal were never written
+            // causal: words past the diagonal were never written; DOC: nor need the words before the first tile be
+            if (i < dmask_nkw(S) && !(CAUSAL && i > (qt >> 1)) && !(DOC && i < (t0 >> 1)))
                 kwds[i] = dmask[dmask_word(bh, S, i, g, myq)];
     }
     f32x4 dq[4];
@@ -625,8 +686,6 @@ __global__ __launch_bounds__(64 * TWB, 3) void attn_bwd_dq_k(const bf16_t* __res
     for (int i = 0; i < 4; ++i) dq[i] = (f32x4){0, 0, 0, 0};
     char* sK = smem;
     char* sV = smem + TK * ROWB;
-    static_assert(TROWS_B == TK, "causal: a workgroup's queries are one key tile, the diagonal one");
-    const int nt = CAUSAL ? qt + 1 : (S + TK - 1) / TK;
     // tile t+1's K / V rows (and key mask) are loaded into registers while tile t computes
     Stager<64 * TWB> a, c;
     float nmk = 0.f;                                         // raw load; scaled / bounded at the store
@@ -636,10 +695,10 @@ __global__ __launch_bounds__(64 * TWB, 3) void attn_bwd_dq_k(const bf16_t* __res
         mk_ok = k < S;
         if (MASK && threadIdx.x < TK) nmk = mrow[min(k, S - 1)];
     };
-    a.load(kb, rs, 0, S);
-    c.load(vb, rs, 0, S);
-    load_mk(0);
-    for (int t = 0; t < nt; ++t) {
+    a.load(kb, rs, t0 * TK, S);
+    c.load(vb, rs, t0 * TK, S);
+    load_mk(t0);
+    for (int t = t0; t < nt; ++t) {
         __syncthreads();
         a.store<true>(sK);
         c.store<false>(sV);
@@ -664,6 +723,7 @@ __global__ __launch_bounds__(64 * TWB, 3) void attn_bwd_dq_k(const bf16_t* __res
         }
         f32x4 ds[4];
         const float lse2 = my_lse * LOG2E;
+        const bool cut = DOC && t * TK < wds;               // per wave: keys before a row's document
         // the forward's keep bits of my query for this tile's keys (one word per 128 keys)
         uint32_t kbits = ~0u;
         if (DROP && qok) {
@@ -681,7 +741,8 @@ __global__ __launch_bounds__(64 * TWB, 3) void attn_bwd_dq_k(const bf16_t* __res
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 // (causal: the diagonal tile hides the keys past the query)
-                const bool ok = qok && k0 + r < S && !(CAUSAL && t == qt && k0 + r > myq);
+                const bool ok = qok && k0 + r < S && !(CAUSAL && t == qt && k0 + r > myq) &&
+                                !(DOC && cut && k0 + r < myds);
                 const float pv = ok ? fast_exp2(sc[blk][r] * c2 + mk[r] - lse2) : 0.f;
                 float dpv = dp[blk][r];
                 if (DROP) dpv = ((kbits >> (4 * blk + r)) & 1u) ? dpv * inv_keep : 0.f;
@@ -1685,6 +1746,47 @@ DDL_API int ddl_attn_causal_bwd(const void* qkv, const void* out, const void* do
     else { if (drp) BWD_DQ(false, true); else BWD_DQ(false, false); }
 #undef BWD_DKV
 #undef BWD_DQ
+    const int rc = (int)hipGetLastError();
+    return rc ? rc : (colsum ? 2 : 0);
+}
+
+// Document-masked causal attention for packed rows: query i attends to keys doc_start[b, i] <= j <= i.
+// The arguments of ddl_attn_causal_fwd / _bwd plus doc_start / doc_end, int32 [B, S]: the row index of the
+// first token of each token's document and the exclusive end of that document (ops.doc_bounds; both
+// non-decreasing along a row, doc_start[b, i] <= i < doc_end[b, i]).  The DOC instances of the tiled causal
+// kernels skip the key tiles before a query tile's earliest document and the query tiles after a key tile's
+// latest one.  There is no key-bias instance: a non-null mask is -7 (the caller composes the reference).
+DDL_API int ddl_attn_doc_fwd(const void* qkv, const float* mask, void* out, float* lse, int B, int S, int H,
+                             float scale, float p_drop, uint64_t seed, uint32_t* dmask, const int* doc_start,
+                             const int* doc_end, hipStream_t st) {
+    if (p_drop > 0.f && !dmask) return -5;
+    if (mask || !doc_start || !doc_end) return -7;
+    if ((S + TROWS_F - 1) / TROWS_F > 65535) return -6;
+    dim3 grid(B * H, (S + TROWS_F - 1) / TROWS_F);      // as ddl_attn_causal_fwd: last query tile first
+#define FWD_DOC(D) attn_fwd_k<false, D, true, true><<<grid, 64 * TWF, 0, st>>>((const bf16_t*)qkv, nullptr, (bf16_t*)out, lse, B, S, H, scale, p_drop, seed, dmask, doc_start)
+    if (p_drop > 0.f) FWD_DOC(true); else FWD_DOC(false);
+#undef FWD_DOC
+    DDL_RETURN_LAUNCH();
+}
+
+// colsum (nullable): always the tiled form, as ddl_attn_causal_bwd; returns 2 when it was written
+DDL_API int ddl_attn_doc_bwd(const void* qkv, const void* out, const void* dout, const float* lse, const float* mask,
+                             float* delta, void* dqkv, int B, int S, int H, float scale, float p_drop,
+                             const uint32_t* dmask, float* colsum, const int* doc_start, const int* doc_end,
+                             hipStream_t st) {
+    if (p_drop > 0.f && !dmask) return -5;
+    if (mask || !doc_start || !doc_end) return -7;
+    if ((S + TROWS_B - 1) / TROWS_B > 65535) return -6;
+    const long rows = (long)B * S * H;
+    attn_delta_k<<<(int)((rows * 8 + 255) / 256), 256, 0, st>>>((const bf16_t*)dout, (const bf16_t*)out, delta, B, S, H);
+    dim3 grid(B * H, (S + TROWS_B - 1) / TROWS_B);
+#define BWD_DOC(DR)                                                                                                    \
+    attn_bwd_dkv_k<DR, true, true><<<grid, 64 * TWB, 0, st>>>((const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,     \
+        nullptr, (bf16_t*)dqkv, B, S, H, scale, p_drop, dmask, colsum, doc_end);                                       \
+    attn_bwd_dq_k<false, DR, true, true><<<grid, 64 * TWB, 0, st>>>((const bf16_t*)qkv, (const bf16_t*)dout, lse,      \
+        delta, nullptr, (bf16_t*)dqkv, B, S, H, scale, p_drop, dmask, colsum, doc_start)
+    if (p_drop > 0.f) { BWD_DOC(true); } else { BWD_DOC(false); }
+#undef BWD_DOC
     const int rc = (int)hipGetLastError();
     return rc ? rc : (colsum ? 2 : 0);
 }

@@ -172,8 +172,12 @@ __device__ __forceinline__ void rope_cs(const float* __restrict__ tab, uint32_t 
     load8(tab + (long)s * 64 + 32 + 8 * j, sn);
 }
 
+// POS: token (b, s) is rotated by table row pos[b, s] (packed rows: the position inside its document) in
+// place of row s; the value is the caller's contract and is clamped into the table all the same.
+template <bool POS>
 __global__ __launch_bounds__(256) void rope_qkv_fwd_k(const bf16_t* __restrict__ in, const float* __restrict__ tab,
-                                                      bf16_t* __restrict__ out, long ntok, RopeDims d) {
+                                                      bf16_t* __restrict__ out, long ntok, RopeDims d,
+                                                      const int* __restrict__ pos, uint32_t n_pos) {
     const long tok0 = (long)blockIdx.x * d.tpb;
     const int nt = (int)min((long)d.tpb, ntok - tok0);
     const uint32_t s0 = (uint32_t)(tok0 % d.S);
@@ -190,7 +194,8 @@ __global__ __launch_bounds__(256) void rope_qkv_fwd_k(const bf16_t* __restrict__
             for (int g = 0; g < d.G; ++g) { st16(o + g * 64, a); st16(o + g * 64 + 32, b); }
             continue;
         }
-        const uint32_t st = s0 + lt, s = st - fdiv(st, d.seq) * d.seq.d;
+        const uint32_t st = s0 + lt;
+        const uint32_t s = POS ? min((uint32_t)pos[tok0 + lt], n_pos - 1) : st - fdiv(st, d.seq) * d.seq.d;
         float c[8], sn[8], x1[8], x2[8], o1[8], o2[8];
         rope_cs(tab, s, j, c, sn);
         unpack8(a, x1);
@@ -215,8 +220,10 @@ __global__ __launch_bounds__(256) void rope_qkv_fwd_k(const bf16_t* __restrict__
 
 // Backward, the same items over the fused projection's gradient: dq rotated by the transpose, dk and dv
 // summed over their group's G query-head slots in fp32 (slot order), the dk sum rotated once.
+template <bool POS>
 __global__ __launch_bounds__(256) void rope_qkv_bwd_k(const bf16_t* __restrict__ dout, const float* __restrict__ tab,
-                                                      bf16_t* __restrict__ din, long ntok, RopeDims d) {
+                                                      bf16_t* __restrict__ din, long ntok, RopeDims d,
+                                                      const int* __restrict__ pos, uint32_t n_pos) {
     const long tok0 = (long)blockIdx.x * d.tpb;
     const int nt = (int)min((long)d.tpb, ntok - tok0);
     const uint32_t s0 = (uint32_t)(tok0 % d.S);
@@ -246,7 +253,8 @@ __global__ __launch_bounds__(256) void rope_qkv_bwd_k(const bf16_t* __restrict__
             for (int e = 0; e < 8; ++e) { g1[e] += t1[e]; g2[e] += t2[e]; }
         }
         if (hin < d.H + d.Hkv) {
-            const uint32_t st = s0 + lt, s = st - fdiv(st, d.seq) * d.seq.d;
+            const uint32_t st = s0 + lt;
+            const uint32_t s = POS ? min((uint32_t)pos[tok0 + lt], n_pos - 1) : st - fdiv(st, d.seq) * d.seq.d;
             float c[8], sn[8];
             rope_cs(tab, s, j, c, sn);
 #pragma unroll
@@ -389,7 +397,7 @@ DDL_API int ddl_rope_qkv_fwd(const void* in, const float* tab, void* out, long B
     if (S > n_pos) return -2;
     const long ntok = B * S, grid = (ntok + d.tpb - 1) / d.tpb;
     if (grid > 0x7fffffffL) return -1;
-    rope_qkv_fwd_k<<<(unsigned)grid, 256, 0, st>>>((const bf16_t*)in, tab, (bf16_t*)out, ntok, d);
+    rope_qkv_fwd_k<false><<<(unsigned)grid, 256, 0, st>>>((const bf16_t*)in, tab, (bf16_t*)out, ntok, d, nullptr, 0);
     DDL_RETURN_LAUNCH();
 }
 
@@ -400,7 +408,31 @@ DDL_API int ddl_rope_qkv_bwd(const void* dout, const float* tab, void* din, long
     if (S > n_pos) return -2;
     const long ntok = B * S, grid = (ntok + d.tpb - 1) / d.tpb;
     if (grid > 0x7fffffffL) return -1;
-    rope_qkv_bwd_k<<<(unsigned)grid, 256, 0, st>>>((const bf16_t*)dout, tab, (bf16_t*)din, ntok, d);
+    rope_qkv_bwd_k<false><<<(unsigned)grid, 256, 0, st>>>((const bf16_t*)dout, tab, (bf16_t*)din, ntok, d, nullptr, 0);
+    DDL_RETURN_LAUNCH();
+}
+
+// The same with explicit positions: pos int32 [B, S], token (b, s) rotated by table row pos[b, s], each in
+// [0, n_pos) (the caller's contract; S itself may exceed n_pos).
+DDL_API int ddl_rope_qkv_pos_fwd(const void* in, const float* tab, void* out, const int* pos, long B, long S, int H,
+                                 int Hkv, long n_pos, hipStream_t st) {
+    RopeDims d;
+    if (!rope_dims(B, S, H, Hkv, d) || !pos || n_pos < 1 || n_pos > 0x7fffffffL) return -1;
+    const long ntok = B * S, grid = (ntok + d.tpb - 1) / d.tpb;
+    if (grid > 0x7fffffffL) return -1;
+    rope_qkv_fwd_k<true><<<(unsigned)grid, 256, 0, st>>>((const bf16_t*)in, tab, (bf16_t*)out, ntok, d, pos,
+                                                         (uint32_t)n_pos);
+    DDL_RETURN_LAUNCH();
+}
+
+DDL_API int ddl_rope_qkv_pos_bwd(const void* dout, const float* tab, void* din, const int* pos, long B, long S, int H,
+                                 int Hkv, long n_pos, hipStream_t st) {
+    RopeDims d;
+    if (!rope_dims(B, S, H, Hkv, d) || !pos || n_pos < 1 || n_pos > 0x7fffffffL) return -1;
+    const long ntok = B * S, grid = (ntok + d.tpb - 1) / d.tpb;
+    if (grid > 0x7fffffffL) return -1;
+    rope_qkv_bwd_k<true><<<(unsigned)grid, 256, 0, st>>>((const bf16_t*)dout, tab, (bf16_t*)din, ntok, d, pos,
+                                                         (uint32_t)n_pos);
     DDL_RETURN_LAUNCH();
 }
 

@@ -77,6 +77,7 @@ class TrainConfig:
     synthetic_pool: int = 4          # distinct device-resident batches cycled
     pad_fraction: float = 0.0        # NLP: random right-padding up to this fraction (attention-mask path)
     mlm_predictions: int = 0         # BERT pretraining: masked-LM prediction slots per sequence (0: none)
+    docs_per_row: int = 0            # causal LM: documents packed into every row (position_ids path; 0: one, unpacked)
 
     # ---------------------------------------------------------------------
     @property
@@ -185,6 +186,8 @@ PRESETS: Dict[str, TrainConfig] = {
                                   optimizer="adamw", lr=3e-3, weight_decay=0.01, betas=[0.9, 0.95], eps=1e-8,
                                   dropout=0.0),
 }
+# the same on packed rows: 8 documents per 2048-token row, isolated by the document-masked attention kernels
+PRESETS["llama_pretrain_packed"] = PRESETS["llama_pretrain"].replace(docs_per_row=8)
 
 
 def get_preset(name: str, **overrides) -> TrainConfig:

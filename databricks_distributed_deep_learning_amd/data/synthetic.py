@@ -71,7 +71,7 @@ class SyntheticTokens:
     def __init__(self, batch_size: int, seq_len: int = 128, vocab_size: int = 30522, num_labels: int = 2,
                  device: Optional[torch.device] = None, rank: int = 0, seed: int = 1234, pool: int = 4,
                  pad_fraction: float = 0.0, steps_per_epoch: int = 0, mlm_predictions: int = 0,
-                 causal_lm: bool = False):
+                 causal_lm: bool = False, docs_per_row: int = 0):
         """``mlm_predictions`` = P > 0 adds the masked-LM pretraining targets to every batch:
         ``masked_lm_positions [B, P]`` (unique per row, ascending, inside the row's unpadded length),
         ``masked_lm_labels [B, P]`` (a random number of trailing slots per row is padding: label
@@ -81,11 +81,24 @@ class SyntheticTokens:
         ``causal_lm`` replaces ``labels`` by the next-token targets ``[B, S]``: ``labels[b, s]`` is
         ``input_ids[b, s + 1]``, -100 at the last position and wherever position ``s + 1`` is padding
         (the shift happens here, not in the model).  It draws nothing, so ids and masks are those of
-        a loader without it."""
+        a loader without it.
+
+        ``docs_per_row`` = k > 0 (with ``causal_lm``) packs k documents into every row: k - 1 distinct
+        random cut points, so every document has at least one token.  The batch gains ``position_ids
+        [B, S]`` (HF's packed-sequence convention: 0 at the first token of every document, previous + 1
+        otherwise) and ``labels`` are -100 at the last token of every document as well.  The cuts come
+        from a generator of their own, so ``input_ids`` are exactly those of a loader without the
+        argument, and with 0 so is the whole batch."""
         self.batch_size, self.seq_len = batch_size, seq_len
         self.device = device or torch.device("cpu")
         self.steps_per_epoch = steps_per_epoch
+        if docs_per_row < 0 or docs_per_row > seq_len:
+            raise ValueError(f"docs_per_row={docs_per_row} must be in 0 .. seq_len ({seq_len})")
+        if docs_per_row > 0 and not causal_lm:
+            raise ValueError("docs_per_row packs causal-LM rows: it needs causal_lm=True")
         g = _gen(self.device, seed * 1000 + rank + 7)
+        # (an offset no rank reaches: seed * 1000 + rank + 7 is the id stream of every rank)
+        g_docs = _gen(self.device, seed * 1000 + rank + 7 + (1 << 40)) if docs_per_row > 0 else None
         self.pool = []
         for _ in range(max(1, pool)):
             ids = torch.randint(0, vocab_size, (batch_size, seq_len), generator=g, device=self.device)
@@ -99,10 +112,27 @@ class SyntheticTokens:
                 labels = torch.full_like(ids, -100)
                 labels[:, :-1] = ids[:, 1:] if mask is None else ids[:, 1:].masked_fill(mask[:, 1:] == 0, -100)
             batch = {"input_ids": ids, "attention_mask": mask, "labels": labels}
+            if docs_per_row > 0:
+                batch["position_ids"] = self._pack(docs_per_row, labels, g_docs)
             if mlm_predictions > 0:
                 batch.update(self._mlm_targets(mlm_predictions, mask, vocab_size, pad_fraction, g))
             self.pool.append(batch)
         self._i = 0
+
+    def _pack(self, k: int, labels: torch.Tensor, g) -> torch.Tensor:
+        """Cut every row into k documents: returns ``position_ids`` and sets ``labels`` (in place) to -100
+        at every document's last token."""
+        B, S, dev = self.batch_size, self.seq_len, self.device
+        # k - 1 distinct starts among 1 .. S-1: the k - 1 smallest of S - 1 random keys
+        start = torch.zeros(B, S, dtype=torch.bool, device=dev)
+        start[:, 0] = True
+        if k > 1:
+            cuts = torch.rand(B, S - 1, generator=g, device=dev).argsort(dim=1)[:, :k - 1] + 1
+            start.scatter_(1, cuts, True)
+        ar = torch.arange(S, device=dev)
+        first = torch.where(start, ar[None, :], torch.zeros_like(ar)[None, :]).cummax(1).values
+        labels[:, :-1].masked_fill_(start[:, 1:], -100)
+        return ar[None, :] - first
 
     def _mlm_targets(self, P: int, mask, vocab_size: int, pad_fraction: float, g) -> dict:
         B, S, dev = self.batch_size, self.seq_len, self.device

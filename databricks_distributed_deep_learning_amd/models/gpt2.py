@@ -138,11 +138,16 @@ class GPT2Block(nn.Module):
             return self.fc2(F.gelu(self.fc1(y), approximate="tanh"), **kw)
         return self.fc2(self.fc1(y), fuse_dgelu=True, **kw)
 
-    def forward(self, h, mask=None):
+    def forward(self, h, mask=None, doc=None):
+        """``doc`` (packed rows): ``ops.doc_bounds``' pair."""
         bridged = torch.is_grad_enabled() and h.requires_grad
         b1 = GradBridge() if bridged else None
         y = self.ln_1(h, grad_from=b1)
-        ctx = ops.attention(self.qkv(y), self.num_heads, mask, self.attn_dropout, self.training, causal=True)
+        if doc is None:
+            ctx = ops.attention(self.qkv(y), self.num_heads, mask, self.attn_dropout, self.training, causal=True)
+        else:
+            ctx = ops.attention(self.qkv(y), self.num_heads, mask, self.attn_dropout, self.training, causal=True,
+                                doc_start=doc)
         if self.dropout.p > 0.0 and self.training:
             h = h + self.dropout(self.attn_out(ctx))
             return h + self.dropout(self._mlp(self.ln_2(h)))
@@ -215,20 +220,34 @@ class GPT2LMHeadModel(nn.Module):
     # ZeRO-1 gather waits (parallel/ddp.py): the root's forward reads both tables directly
     _ddl_direct_reads = ("wte", "wpe")
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, position_ids=None):
         """``token_type_ids`` is ignored (GPT-2 has none): it keeps the training loop's
         ``(input_ids, attention_mask, token_type_ids, labels)`` call form.
         Returns ``(loss, None)`` with labels -- the fused head never hands out the logits -- and the
-        ``[B, S, vocab]`` logits without."""
+        ``[B, S, vocab]`` logits without.
+
+        ``position_ids`` (int ``[B, S]``, HF's packed-sequence convention: 0 at the first token of every
+        document, previous + 1 otherwise) makes each row several documents: ``wpe`` is read at these
+        positions and no token attends across a boundary.  The caller sets the label of each document's last
+        token to -100."""
         B, S = input_ids.shape
         if S > self.config.n_positions:
             raise ValueError(f"sequence length {S} exceeds n_positions {self.config.n_positions}")
         mask_bias = None
         if attention_mask is not None:
             mask_bias = (1.0 - attention_mask.float()) * -10000.0
-        h = self.drop(self.wte(input_ids) + self.wpe.weight[:S].unsqueeze(0))
-        for blk in self.h:
-            h = blk(h, mask_bias)
+        if position_ids is None:
+            h = self.drop(self.wte(input_ids) + self.wpe.weight[:S].unsqueeze(0))
+            for blk in self.h:
+                h = blk(h, mask_bias)
+        else:
+            if position_ids.shape != input_ids.shape or position_ids.device != input_ids.device:
+                raise ValueError(f"position_ids {tuple(position_ids.shape)} on {position_ids.device} must match "
+                                 f"input_ids {(B, S)} on {input_ids.device}")
+            doc = ops.doc_bounds(position_ids)          # checked once per batch: positions < S <= n_positions
+            h = self.drop(self.wte(input_ids) + self.wpe(position_ids))
+            for blk in self.h:
+                h = blk(h, mask_bias, doc)
         h = self.ln_f(h)
         if labels is not None:
             loss = ops.linear_cross_entropy(h.reshape(-1, h.shape[-1]), self.wte.weight, None, labels.reshape(-1),

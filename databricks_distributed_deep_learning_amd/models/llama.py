@@ -139,12 +139,17 @@ class LlamaBlock(nn.Module):
         self.gate_up = Linear(E, 2 * c.intermediate_size, bias=False, init_std=std)
         self.down_proj = Linear(c.intermediate_size, E, bias=False, init_std=std)
 
-    def forward(self, h, table, mask=None):
+    def forward(self, h, table, mask=None, positions=None, doc=None):
+        """``positions`` / ``doc`` (packed rows): the int32 rotary positions and ``ops.doc_bounds``' pair."""
         bridged = torch.is_grad_enabled() and h.requires_grad
         b1 = GradBridge() if bridged else None
         y = self.input_layernorm(h, grad_from=b1)
-        qkv = ops.rope_qkv(self.qkv(y), table, self.num_heads, self.num_kv_heads)
-        ctx = ops.attention(qkv, self.num_heads, mask, 0.0, self.training, causal=True)
+        if doc is None:
+            qkv = ops.rope_qkv(self.qkv(y), table, self.num_heads, self.num_kv_heads)
+            ctx = ops.attention(qkv, self.num_heads, mask, 0.0, self.training, causal=True)
+        else:
+            qkv = ops.rope_qkv(self.qkv(y), table, self.num_heads, self.num_kv_heads, positions=positions)
+            ctx = ops.attention(qkv, self.num_heads, mask, 0.0, self.training, causal=True, doc_start=doc)
         h = self.o_proj(ctx, residual=h, residual_grad_to=b1)
         b2 = GradBridge() if bridged else None
         y = self.post_attention_layernorm(h, grad_from=b2)
@@ -229,10 +234,14 @@ class LlamaForCausalLM(nn.Module):
     def head_weight(self) -> torch.Tensor:
         return self.embed_tokens.weight if self.lm_head is None else self.lm_head.weight
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, position_ids=None):
         """``token_type_ids`` is ignored: it keeps the training loop's ``(input_ids, attention_mask,
         token_type_ids, labels)`` call form.  Returns ``(loss, None)`` with labels -- the fused head never
-        hands out the logits -- and the ``[B, S, vocab]`` logits without."""
+        hands out the logits -- and the ``[B, S, vocab]`` logits without.
+
+        ``position_ids`` (int ``[B, S]``, HF's packed-sequence convention: 0 at the first token of every
+        document, previous + 1 otherwise) makes each row several documents: rotary positions restart and no
+        token attends across a boundary.  The caller sets the label of each document's last token to -100."""
         B, S = input_ids.shape
         if S > self.config.max_position_embeddings:
             raise ValueError(f"sequence length {S} exceeds max_position_embeddings "
@@ -241,8 +250,17 @@ class LlamaForCausalLM(nn.Module):
         if attention_mask is not None:
             mask_bias = (1.0 - attention_mask.float()) * -10000.0
         h = self.embed_tokens(input_ids)
-        for blk in self.layers:
-            h = blk(h, self.rope_table, mask_bias)
+        if position_ids is None:
+            for blk in self.layers:
+                h = blk(h, self.rope_table, mask_bias)
+        else:
+            if position_ids.shape != input_ids.shape or position_ids.device != input_ids.device:
+                raise ValueError(f"position_ids {tuple(position_ids.shape)} on {position_ids.device} must match "
+                                 f"input_ids {(B, S)} on {input_ids.device}")
+            doc = ops.doc_bounds(position_ids)          # checked once per batch: positions < S <= the table's rows
+            positions = position_ids.to(torch.int32).contiguous()
+            for blk in self.layers:
+                h = blk(h, self.rope_table, mask_bias, positions, doc)
         h = self.norm(h)
         w = self.head_weight()
         if labels is not None:

@@ -16,6 +16,7 @@ from .norm import batch_norm, batch_norm_add_bn, bn_relu_maxpool, layer_norm  # 
 from .linear import linear, linear_small_m  # noqa: F401
 from .activation import gelu, dropout, relu  # noqa: F401
 from .attention import attention, attention_decode, attention_extend, kv_cache_fill  # noqa: F401
+from .attention import doc_bounds  # noqa: F401
 from .attention import attention_decode_gqa, attention_extend_gqa, kv_cache_fill_gqa  # noqa: F401
 from .decode import decode_embed, next_token, next_token_params  # noqa: F401
 from .loss import cross_entropy, softmax_topk  # noqa: F401

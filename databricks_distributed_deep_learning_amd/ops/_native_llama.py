@@ -15,6 +15,9 @@ _lib.register({
     "ddl_rope_qkv_supported": [I, I, I],
     "ddl_rope_qkv_fwd": [P, P, P, L, L, I, I, L, P],
     "ddl_rope_qkv_bwd": [P, P, P, L, L, I, I, L, P],
+    # explicit positions (packed rows): the same + pos int32 [B, S]
+    "ddl_rope_qkv_pos_fwd": [P, P, P, P, L, L, I, I, L, P],
+    "ddl_rope_qkv_pos_bwd": [P, P, P, P, L, L, I, I, L, P],
     "ddl_swiglu_supported": [L, I],
     "ddl_swiglu_fwd": [P, P, L, I, P],
     "ddl_swiglu_bwd": [P, P, P, L, I, P],
@@ -72,34 +75,43 @@ def rms_norm(x, weight, eps, grad_from=None):
 # ------------------------------------------------------------------ RoPE + GQA pack
 class _RopeQKV(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, table, H, Hkv):
+    def forward(ctx, qkv, table, H, Hkv, positions=None):
         qkv = qkv.contiguous()
         table = table.contiguous()
         B, S, _ = qkv.shape
         out = torch.empty(B, S, 3 * H * 64, dtype=qkv.dtype, device=qkv.device)
-        if B * S:
+        if positions is not None:
+            positions = positions.contiguous()
+            if B * S:
+                call("ddl_rope_qkv_pos_fwd", p(qkv), p(table), p(out), p(positions), B, S, H, Hkv, table.shape[0])
+        elif B * S:
             call("ddl_rope_qkv_fwd", p(qkv), p(table), p(out), B, S, H, Hkv, table.shape[0])
         ctx.dims = (B, S, H, Hkv)
-        ctx.save_for_backward(table)
+        ctx.save_for_backward(table, positions)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        table, = ctx.saved_tensors
+        table, positions = ctx.saved_tensors
         B, S, H, Hkv = ctx.dims
         dout = dout.contiguous()
         din = torch.empty(B, S, (H + 2 * Hkv) * 64, dtype=dout.dtype, device=dout.device)
-        if B * S:
+        if positions is not None:
+            if B * S:
+                call("ddl_rope_qkv_pos_bwd", p(dout), p(table), p(din), p(positions), B, S, H, Hkv, table.shape[0])
+        elif B * S:
             call("ddl_rope_qkv_bwd", p(dout), p(table), p(din), B, S, H, Hkv, table.shape[0])
-        return din, None, None, None
+        return din, None, None, None, None
 
 
 def rope_qkv_supported(H: int, Hkv: int, head_dim: int) -> bool:
     return bool(_lib.fn("ddl_rope_qkv_supported")(H, Hkv, head_dim))
 
 
-def rope_qkv(qkv, table, H, Hkv):
-    return _RopeQKV.apply(qkv, table, H, Hkv)
+def rope_qkv(qkv, table, H, Hkv, positions=None):
+    if positions is None:
+        return _RopeQKV.apply(qkv, table, H, Hkv)
+    return _RopeQKV.apply(qkv, table, H, Hkv, positions)
 
 
 # ------------------------------------------------------------------ SwiGLU

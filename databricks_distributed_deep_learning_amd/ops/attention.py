@@ -10,6 +10,7 @@ keep, large negative for padding), the HF extended-attention-mask convention.
 from __future__ import annotations
 
 import math
+import warnings
 from typing import Optional
 
 import torch
@@ -17,9 +18,50 @@ import torch.nn.functional as F
 
 from . import _lib
 
+_warned_mask_doc = False
+
+
+def doc_bounds(position_ids: torch.Tensor):
+    """Document bounds of packed rows from HF-style ``position_ids`` (int ``[B, S]``): every row starts at 0
+    and every further entry is the previous one plus 1, or 0 where a new document starts (``ValueError``
+    otherwise).  Returns ``(doc_start, doc_end)``, int32 ``[B, S]`` on the same device: the row index of the
+    first token of each token's document (``i - position_ids[b, i]``) and the exclusive end of that document.
+    ``ops.attention(..., causal=True, doc_start=...)`` takes the first, or the pair as it is.
+
+    The check reads the device once (a host synchronisation), so call it once per batch, not per layer."""
+    pos = position_ids
+    if pos.dim() != 2 or pos.dtype not in (torch.int32, torch.int64) or pos.shape[1] < 1:
+        raise ValueError(f"position_ids must be an int32 / int64 [B, S >= 1] tensor, got {pos.dtype} "
+                         f"{tuple(pos.shape)}")
+    B, S = pos.shape
+    ok = (pos[:, 0] == 0).all() & ((pos[:, 1:] == pos[:, :-1] + 1) | (pos[:, 1:] == 0)).all()
+    if not bool(ok):
+        raise ValueError("position_ids must start every row at 0 and continue with previous + 1, or 0 where a "
+                         "new document starts")
+    ar = torch.arange(S, device=pos.device)
+    doc_start = (ar[None, :] - pos).to(torch.int32).contiguous()
+    # the end of token i's document: the first start after i, S without one
+    nxt = torch.where(pos == 0, ar[None, :], torch.full_like(pos, S))
+    nxt = torch.cat([nxt[:, 1:], torch.full_like(nxt[:, :1], S)], 1)
+    doc_end = nxt.flip(1).cummin(1).values.flip(1).to(torch.int32).contiguous()
+    return doc_start, doc_end
+
+
+def _doc_pair(doc_start, qkv):
+    """``doc_start`` as ``ops.attention`` takes it -- the int32 ``[B, S]`` tensor or ``doc_bounds``' pair, on
+    ``qkv``'s device -- as ``(doc_start, doc_end or None)``."""
+    B, S = qkv.shape[:2]
+    ds, de = doc_start if isinstance(doc_start, (tuple, list)) else (doc_start, None)
+    for t in (ds, de):
+        if t is not None and (t.dtype != torch.int32 or t.shape != (B, S) or t.device != qkv.device):
+            raise ValueError(f"doc_start must be int32 [B={B}, S={S}] on {qkv.device}, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    return ds, de
+
 
 def attention_reference(qkv: torch.Tensor, num_heads: int, mask: Optional[torch.Tensor] = None,
-                        dropout_p: float = 0.0, training: bool = False, causal: bool = False) -> torch.Tensor:
+                        dropout_p: float = 0.0, training: bool = False, causal: bool = False,
+                        doc_start=None) -> torch.Tensor:
     B, S, three_hd = qkv.shape
     hd = three_hd // 3
     D = hd // num_heads
@@ -30,6 +72,13 @@ def attention_reference(qkv: torch.Tensor, num_heads: int, mask: Optional[torch.
     tri = None
     if causal:      # -inf above the diagonal, [S, S]
         tri = torch.full((S, S), float("-inf"), device=q.device, dtype=torch.float32).triu(1)
+    if doc_start is not None:
+        if not causal:
+            raise ValueError("doc_start masks packed causal rows: it needs causal=True")
+        ds = _doc_pair(doc_start, qkv)[0]
+        # -inf on the keys before the query's document as well, [B, 1, S, S]
+        before = torch.arange(S, device=q.device).view(1, 1, 1, S) < ds.view(B, 1, S, 1)
+        tri = tri.expand(B, 1, S, S).masked_fill(before, float("-inf"))
     if q.is_cuda:
         if tri is not None:     # one combined mask (SDPA takes either is_causal or attn_mask)
             attn_mask = tri.to(q.dtype) if attn_mask is None else attn_mask + tri.to(q.dtype)
@@ -50,11 +99,36 @@ def attention_reference(qkv: torch.Tensor, num_heads: int, mask: Optional[torch.
 
 
 def attention(qkv: torch.Tensor, num_heads: int, mask: Optional[torch.Tensor] = None,
-              dropout_p: float = 0.0, training: bool = False, *, causal: bool = False) -> torch.Tensor:
+              dropout_p: float = 0.0, training: bool = False, *, causal: bool = False,
+              doc_start=None) -> torch.Tensor:
+    """``doc_start`` (with ``causal=True``): packed rows.  int32 ``[B, S]`` on the tensors' device, the row
+    index of the first token of each token's document; query i then sees key j iff
+    ``doc_start[b, i] <= j <= i``.  ``ops.doc_bounds`` builds it from ``position_ids``, and only what it
+    returns is supported: non-decreasing along a row with ``doc_start[b, i] <= i``.  That is not checked here
+    (it would cost a host synchronisation per layer); the kernels take their loop bounds from a workgroup's
+    first row, so a tensor that breaks it is memory-safe but gives other results than the reference.  The
+    ``(doc_start, doc_end)`` pair may be passed as it is, which spares the native path deriving the ends on
+    every call.  There is no native kernel for ``mask`` together with ``doc_start``: that combination takes
+    the reference composition, an ``[B, 1, S, S]`` mask per call, and warns once (in a packed row the unused
+    tail is a document of its own whose labels are -100, so no key bias is needed)."""
+    if doc_start is not None and not causal:
+        raise ValueError("doc_start masks packed causal rows: it needs causal=True")
     if _lib.use_native(qkv):
-        from . import _native_attention
-        return _native_attention.attention(qkv, num_heads, mask, dropout_p if training else 0.0, causal)
-    return attention_reference(qkv, num_heads, mask, dropout_p, training, causal=causal)
+        if doc_start is None:
+            from . import _native_attention
+            return _native_attention.attention(qkv, num_heads, mask, dropout_p if training else 0.0, causal)
+        ds, de = _doc_pair(doc_start, qkv)
+        if mask is None:
+            from . import _native_attention
+            return _native_attention.attention(qkv, num_heads, None, dropout_p if training else 0.0, True,
+                                               doc=(ds, de))
+        global _warned_mask_doc
+        if not _warned_mask_doc:
+            _warned_mask_doc = True
+            warnings.warn("ops.attention: a key bias (attention_mask) together with doc_start has no HIP kernel and "
+                          "runs the reference attention with an [B, 1, S, S] mask; packed rows need no "
+                          "attention_mask", RuntimeWarning, stacklevel=2)
+    return attention_reference(qkv, num_heads, mask, dropout_p, training, causal=causal, doc_start=doc_start)
 
 
 # ------------------------------------------------------------------ decode (one new token per sequence, KV cache)

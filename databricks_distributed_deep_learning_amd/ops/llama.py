@@ -11,6 +11,8 @@ kernels do not cover); bf16 GPU tensors take the HIP kernels of ``csrc/kernels/l
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 import torch.nn.functional as F
 
@@ -55,7 +57,7 @@ def rope_table(n_positions: int, theta: float, head_dim: int = 64, device=None) 
     return table if device is None else table.to(device)
 
 
-def _rope_check(qkv, table, num_heads, num_kv_heads):
+def _rope_check(qkv, table, num_heads, num_kv_heads, positions=None):
     if qkv.dim() != 3:
         raise ValueError("rope_qkv takes the fused projection [B, S, (H + 2 Hkv) D]")
     if num_kv_heads < 1 or num_heads % num_kv_heads:
@@ -66,19 +68,30 @@ def _rope_check(qkv, table, num_heads, num_kv_heads):
     D = W // (num_heads + 2 * num_kv_heads)
     if table.dim() != 2 or table.shape[1] != D:
         raise ValueError(f"table must be [n_positions, {D}], got {tuple(table.shape)}")
-    if qkv.shape[1] > table.shape[0]:
-        raise ValueError(f"sequence length {qkv.shape[1]} exceeds the rotary table's {table.shape[0]} positions")
+    if positions is None:
+        if qkv.shape[1] > table.shape[0]:
+            raise ValueError(f"sequence length {qkv.shape[1]} exceeds the rotary table's {table.shape[0]} positions")
+    elif positions.dtype != torch.int32 or positions.shape != qkv.shape[:2]:
+        raise ValueError(f"positions must be int32 {tuple(qkv.shape[:2])}, got {positions.dtype} "
+                         f"{tuple(positions.shape)}")
     return D
 
 
-def rope_qkv_reference(qkv: torch.Tensor, table: torch.Tensor, num_heads: int, num_kv_heads: int) -> torch.Tensor:
-    D = _rope_check(qkv, table, num_heads, num_kv_heads)
+def rope_qkv_reference(qkv: torch.Tensor, table: torch.Tensor, num_heads: int, num_kv_heads: int,
+                       positions: Optional[torch.Tensor] = None) -> torch.Tensor:
+    D = _rope_check(qkv, table, num_heads, num_kv_heads, positions)
     B, S, _ = qkv.shape
     H, Hkv, half = num_heads, num_kv_heads, D // 2
     ct = _compute_dtype(qkv)
     x = qkv.to(ct).view(B, S, H + 2 * Hkv, D)
-    cos = table[:S, :half].to(ct).view(1, S, 1, half)
-    sin = table[:S, half:].to(ct).view(1, S, 1, half)
+    if positions is None:
+        cos = table[:S, :half].to(ct).view(1, S, 1, half)
+        sin = table[:S, half:].to(ct).view(1, S, 1, half)
+    else:
+        if B * S and not (0 <= int(positions.min()) and int(positions.max()) < table.shape[0]):
+            raise ValueError(f"positions must lie in [0, {table.shape[0]}), the rotary table's rows")
+        row = table[positions.long()].to(ct)                    # [B, S, D]
+        cos, sin = row[:, :, None, :half], row[:, :, None, half:]
 
     def rot(t):
         a, b = t[..., :half], t[..., half:]
@@ -90,13 +103,18 @@ def rope_qkv_reference(qkv: torch.Tensor, table: torch.Tensor, num_heads: int, n
     return torch.stack([q, k, v], 2).reshape(B, S, 3 * H * D).to(qkv.dtype)
 
 
-def rope_qkv(qkv: torch.Tensor, table: torch.Tensor, num_heads: int, num_kv_heads: int) -> torch.Tensor:
-    D = _rope_check(qkv, table, num_heads, num_kv_heads)
-    if _lib.use_native(qkv, table) and qkv.dtype == torch.bfloat16 and table.dtype == torch.float32:
+def rope_qkv(qkv: torch.Tensor, table: torch.Tensor, num_heads: int, num_kv_heads: int,
+             positions: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``positions`` (int32 ``[B, S]``, packed rows): token (b, s) is rotated by table row
+    ``positions[b, s]`` in place of row s, forward and backward.  A value outside the table is a
+    ``ValueError`` on the reference path; on the native path it is the caller's contract
+    (``ops.doc_bounds`` checks ``position_ids`` once per batch: a valid one never passes s)."""
+    D = _rope_check(qkv, table, num_heads, num_kv_heads, positions)
+    if _lib.use_native(qkv, table, positions) and qkv.dtype == torch.bfloat16 and table.dtype == torch.float32:
         from . import _native_llama
         if _native_llama.rope_qkv_supported(num_heads, num_kv_heads, D):
-            return _native_llama.rope_qkv(qkv, table, num_heads, num_kv_heads)
-    return rope_qkv_reference(qkv, table, num_heads, num_kv_heads)
+            return _native_llama.rope_qkv(qkv, table, num_heads, num_kv_heads, positions)
+    return rope_qkv_reference(qkv, table, num_heads, num_kv_heads, positions)
 
 
 # ------------------------------------------------------------------ SwiGLU

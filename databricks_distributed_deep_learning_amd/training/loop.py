@@ -154,7 +154,8 @@ class Trainer:
         vocab = min(c.vocab_size, getattr(mc, "vocab_size", c.vocab_size))
         return SyntheticTokens(c.batch_size, c.seq_len, vocab, c.num_classes, self.device,
                                rank=self.rank, seed=c.seed, pool=c.synthetic_pool, pad_fraction=c.pad_fraction,
-                               mlm_predictions=c.mlm_predictions, causal_lm=c.model.startswith(("gpt", "llama", "smollm")))
+                               mlm_predictions=c.mlm_predictions, causal_lm=c.model.startswith(("gpt", "llama", "smollm")),
+                               docs_per_row=c.docs_per_row)
 
     def _auto_batch(self) -> int:
         from ..utils.memory import fit_batch_size
@@ -181,6 +182,10 @@ class Trainer:
                 raise ValueError(f"{self.cfg.model} trains on masked-LM targets: set mlm_predictions > 0")
             loss, _ = self.model(batch["input_ids"], batch.get("attention_mask"), None, batch["masked_lm_positions"],
                                  batch["masked_lm_labels"], batch["next_sentence_label"])
+            return loss
+        if "position_ids" in batch:      # packed rows (docs_per_row > 0)
+            loss, _ = self.model(batch["input_ids"], batch.get("attention_mask"), None, batch["labels"],
+                                 position_ids=batch["position_ids"])
             return loss
         loss, _ = self.model(batch["input_ids"], batch.get("attention_mask"), None, batch["labels"])
         return loss
