@@ -4,7 +4,7 @@ decode kernels against what the library had before them.
 
     python benchmarks/gpt2_generate_bench.py [--model gpt2] [--prompt 128] [--new 128] [--batches 1,8,16]
                                              [--reps 3] [--skip-e2e] [--skip-recompute] [--skip-glue]
-                                             [--skip-kernels]
+                                             [--skip-sampling] [--skip-kernels]
 
 End to end (bf16, random weights, greedy, no eos): ``generate`` (prefill + cached decode steps), the same
 with ``use_graph=True`` (the decode step captured once and replayed; the capture is timed once, apart) and
@@ -13,7 +13,8 @@ host clock around work that ends in a device synchronise; the best of ``--reps``
 run of each arm, the arms alternating in one process.
 
 The step's glue (``ops.decode_embed``, ``ops.next_token``) at V = 50257 and B in {1, 16} against the ATen
-sequences it replaces, as call times.
+sequences it replaces, as call times; ``next_token`` with top-p, min-p and a repetition penalty against the
+torch composition of the same semantics (``bench_sampling``).
 
 Per kernel, timed by device events around ITERS back-to-back calls (so launch overhead is included:
 "call time"), every call on another copy of its large operand (copies totalling >= 512 MB, more than the
@@ -235,6 +236,49 @@ def bench_glue(dev):
                               "faster_than_aten": bool(t_o < t_a)}), flush=True)
 
 
+def bench_sampling(dev):
+    """``next_token`` with top-p / min-p / a repetition penalty at V = 50257 against the torch composition of the
+    same semantics (``ops.decode``'s ``penalise_logits`` and ``sampling_kept``, then ``torch.multinomial``); the
+    arms alternate, best of 3.  ``plain top-50`` is the unchanged entry point: what top-p's 16 passes add."""
+    import torch
+    from databricks_distributed_deep_learning_amd import ops
+    from databricks_distributed_deep_learning_amd.ops.decode import penalise_logits, sampling_kept
+    V, Lh = 50257, 128
+    for B in (1, 16):
+        logits = (torch.randn(B, V, device=dev) * 2).bfloat16()
+        u = torch.rand(1, B, device=dev)
+        out = torch.zeros(B, dtype=torch.int64, device=dev)
+        history = torch.randint(0, V, (B, Lh), device=dev)
+        history_lens = torch.full((B,), Lh, dtype=torch.int32, device=dev)
+        inv_t = 1.0 / 0.8
+        cases = [("plain top-50", dict(top_k=50), False), ("top_p=0.9", dict(top_p=0.9), False),
+                 ("top-50 + top_p=0.9", dict(top_k=50, top_p=0.9), False), ("min_p=0.05", dict(min_p=0.05), False),
+                 ("repetition_penalty=1.2, 128 ids", dict(repetition_penalty=1.2), True)]
+        for name, kw, hist in cases:
+            params = ops.next_token_params(inv_t, kw.get("top_k"), device=dev,
+                                           **{k: v for k, v in kw.items() if k != "top_k"})
+            h = dict(history=history, history_lens=history_lens) if hist else {}
+
+            def ours(i):
+                ops.next_token(logits, u=u, params=params, out=out, **h)
+
+            def composed(i):
+                x = penalise_logits(logits, kw["repetition_penalty"], history, history_lens, None, None) if hist \
+                    else logits
+                x = x.float()
+                kept = sampling_kept(x, inv_t, kw.get("top_k"), kw.get("top_p", 1.0), kw.get("min_p", 0.0))
+                z = torch.where(kept, x * inv_t, torch.full_like(x, float("-inf")))
+                torch.multinomial(torch.softmax(z, -1), 1)
+
+            with torch.no_grad():
+                t_o = t_a = float("inf")
+                for _ in range(3):
+                    t_o = min(t_o, _best(ours, 400, 1))
+                    t_a = min(t_a, _best(composed, 100, 1))
+            print(json.dumps({"kernel": "next_token " + name, "B": B, "V": V, "us": round(t_o, 2),
+                              "torch_us": round(t_a, 2), "torch_over_ours": round(t_a / t_o, 2)}), flush=True)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2")
@@ -246,6 +290,7 @@ def main() -> int:
     ap.add_argument("--skip-kernels", action="store_true")
     ap.add_argument("--skip-recompute", action="store_true", help="end to end: the cached and graph arms only")
     ap.add_argument("--skip-glue", action="store_true")
+    ap.add_argument("--skip-sampling", action="store_true")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -255,6 +300,8 @@ def main() -> int:
         bench_e2e(dev, args)
     if not args.skip_glue:
         bench_glue(dev)
+    if not args.skip_sampling:
+        bench_sampling(dev)
     if not args.skip_kernels:
         bench_attention(dev)
         bench_linear(dev)

@@ -5,6 +5,7 @@
 //   ddl_next_token     logits [B, V] bf16 -> one token per row (argmax, or temperature / top-k sampling from
 //                      a given uniform number), the eos / pad rule, and the advance of the step's device
 //                      state (token fed to the next step, output column, step counter, cache lengths).
+//   ddl_next_token_ex  the same with a repetition penalty, top-p and min-p: next_token_ex_k, further down.
 //
 // ddl_next_token: one 1024-thread workgroup per row.  The row is read from memory once, as 16-byte pieces,
 // into LDS as ordered 16-bit keys (key order == value order, so the k-th largest VALUE is the k-th largest
@@ -232,6 +233,236 @@ __global__ __launch_bounds__(NT_THREADS) void next_token_k(const bf16_t* __restr
     }
 }
 
+// ---- next_token_ex_k: next_token_k with a repetition penalty, top-p and min-p.  Its own kernel, so that
+// next_token_k's instances compile as they always did; with the three settings off it does what that one does.
+// params int32 [8]: the five slots above, then the fp32 bits of
+//   [5] top_p (1: off)  [6] min_p (0: off)  [7] repetition_penalty (1: off)
+// Order: penalty, (temperature,) top-k, top-p, min-p.  Each of the three filters is "key >= a threshold", so the
+// kept set is still one key threshold: the largest of the three.
+//   penalty  x_j <- x_j / r (x_j > 0) or x_j * r, in fp32 from the logit in memory, rounded once to bf16, for every
+//            column id in history[b, :history_lens[b]] and tokens_out[b, :step[b]]; ids outside [0, V) are
+//            skipped.  The new key is stored over the column's key in LDS: a column listed twice gets the same
+//            value twice, so the stores need no order.  LDS-resident rows only (the other loader re-reads
+//            memory; its caller penalises the logits itself and passes r = 1).
+//   top-p    the largest key T with mass(key >= T) >= p W, W and the masses over the top-k set: the 16-step
+//            bisection of top-k with a block-wide fp32 sum in place of the count, every sum in one fixed order
+//            (the thread's run, a butterfly over the wave, the waves in index order), hence repeatable, and
+//            monotone in T because fp32 addition of non-negative terms is.
+//   min-p    the smallest key whose value x has (x - max) * inv_t >= log(min_p) in fp32: the predicate is
+//            monotone in the key, so every thread bisects it in registers, with no pass over the row.
+constexpr int PRM_TOPP = 5, PRM_MINP = 6, PRM_PEN = 7, PRM_EX = 8;
+
+__device__ __forceinline__ float wave_sum_f(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);     // a + b == b + a: every lane gets the same bits
+    return v;
+}
+
+template <bool LDS_ROW>
+__global__ __launch_bounds__(NT_THREADS) void next_token_ex_k(const bf16_t* __restrict__ logits, int V, int R,
+                                                              const float* __restrict__ u, int Tu,
+                                                              const int* __restrict__ params, int n_params,
+                                                              const int64_t* __restrict__ history, int Lh,
+                                                              const int* __restrict__ history_lens, int* step,
+                                                              uint8_t* done, int64_t* tok_out, int64_t* tokens_out,
+                                                              int To, int* lens) {
+    extern __shared__ uint4 row_lds[];
+    __shared__ uint32_t red_hi[NT_WAVES], red_lo[NT_WAVES];
+    __shared__ int red_cnt[2][NT_WAVES], red_min[NT_WAVES], red_max[NT_WAVES];
+    __shared__ float red_w[NT_WAVES], red_m[2][NT_WAVES];
+
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int step0 = step ? step[b] : 0;       // read once, before anything of this row is written
+    const bf16_t* rowp = logits + (long)b * V;
+    Row<LDS_ROW> row;
+    row.lo = (int)((reinterpret_cast<uintptr_t>(rowp) >> 1) & 7);
+    row.hi = row.lo + V;
+    row.base = rowp - row.lo;
+    row.lds = reinterpret_cast<const uint16_t*>(row_lds);
+    const int p_first = tid * R, p_last = std::min(p_first + R, row.hi);
+
+    const bool ex = params != nullptr && n_params >= PRM_EX;
+    const float top_p = ex ? __int_as_float(params[PRM_TOPP]) : 1.f;
+    const float min_p = ex ? __int_as_float(params[PRM_MINP]) : 0.f;
+    const float pen = ex ? __int_as_float(params[PRM_PEN]) : 1.f;
+    const bool penalise = LDS_ROW && pen != 1.f && pen > 0.f;      // (uniform over the workgroup)
+
+    // ---- pass 1: the row into LDS as keys; the maximum, ties to the lowest slot.
+    // (key + 1, 0x7fffffff - p) ordered lexicographically; (0, 0) = nothing seen
+    uint32_t bk = 0, bp = 0;
+    if (!penalise) {
+        for (int p0 = p_first; p0 < p_last; p0 += 8) {
+            if (p0 + 8 <= row.lo) continue;
+            const uint4 k8 = Row<LDS_ROW>::to_keys(row.raw(p0));
+            if (LDS_ROW) row_lds[p0 >> 3] = k8;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int p = p0 + e;
+                const uint32_t key = key_of(k8, e) + 1;
+                if (p >= row.lo && p < row.hi && key > bk) { bk = key; bp = 0x7fffffffu - (uint32_t)p; }
+            }
+        }
+    } else {
+        for (int p0 = p_first; p0 < p_last; p0 += 8) {
+            if (p0 + 8 <= row.lo) continue;
+            row_lds[p0 >> 3] = Row<LDS_ROW>::to_keys(row.raw(p0));
+        }
+        __syncthreads();
+        // the penalised columns' keys over the row's; then the maximum, from LDS
+        uint16_t* keys16 = reinterpret_cast<uint16_t*>(row_lds);
+        const int n_h = history ? std::min(std::max(history_lens ? history_lens[b] : Lh, 0), Lh) : 0;
+        const int n_g = tokens_out && step ? std::min(std::max(step0, 0), To) : 0;
+        for (int i = tid; i < n_h + n_g; i += NT_THREADS) {
+            const int64_t id = i < n_h ? history[(long)b * Lh + i] : tokens_out[(long)b * To + (i - n_h)];
+            if (id < 0 || id >= V) continue;
+            const float x = bf2f(rowp[id]);
+            keys16[row.lo + (int)id] = (uint16_t)bf_key(f2bf(x > 0.f ? __fdiv_rn(x, pen) : x * pen));
+        }
+        __syncthreads();
+        FOR_RUN(if (key + 1 > bk) { bk = key + 1; bp = 0x7fffffffu - (uint32_t)p; })
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t ok = __shfl_xor(bk, o, 64), op = __shfl_xor(bp, o, 64);
+        if (ok > bk || (ok == bk && op > bp)) { bk = ok; bp = op; }
+    }
+    if (lane == 0) { red_hi[wave] = bk; red_lo[wave] = bp; }
+    __syncthreads();        // also: the row's keys are in LDS
+#pragma unroll
+    for (int w = 0; w < NT_WAVES; ++w) {
+        const uint32_t ok = red_hi[w], op = red_lo[w];
+        if (ok > bk || (ok == bk && op > bp)) { bk = ok; bp = op; }
+    }
+    int pick = (int)(0x7fffffffu - bp);         // the argmax slot
+
+    const bool sample = u != nullptr && (params == nullptr || params[PRM_SAMPLE] != 0);
+    if (sample) {
+        const float inv_t = params ? __int_as_float(params[PRM_INVT]) : 1.f;
+        const int top_k = params ? params[PRM_TOPK] : 0;
+        const float xmax = key_val(bk - 1);
+
+        // ---- the k-th largest key: the largest T with count(key >= T) >= k
+        uint32_t thr = 0;
+        if (top_k > 0 && top_k < V) {
+            for (int bit = 15; bit >= 0; --bit) {
+                const uint32_t cand = thr | (1u << bit);
+                int c = 0;
+                FOR_RUN(c += key >= cand ? 1 : 0;)
+                c = wave_sum_i(c);
+                int* rc = red_cnt[bit & 1];     // two buffers: one barrier per step
+                if (lane == 0) rc[wave] = c;
+                __syncthreads();
+                int tot = 0;
+#pragma unroll
+                for (int w = 0; w < NT_WAVES; ++w) tot += rc[w];
+                if (tot >= top_k) thr = cand;
+            }
+        }
+
+        // ---- top-p: the largest T with mass(key >= max(T, thr)) >= p W.  Up to T = thr that mass is W itself
+        // (the same terms in the same order) and p <= 1, so the search never ends below thr.
+        if (top_p < 1.f) {
+            float m = 0.f;
+            FOR_RUN(if (key >= thr) m += __expf((key_val(key) - xmax) * inv_t);)
+            m = wave_sum_f(m);
+            if (lane == 0) red_w[wave] = m;
+            __syncthreads();
+            float need = 0.f;
+#pragma unroll
+            for (int w = 0; w < NT_WAVES; ++w) need += red_w[w];
+            need *= top_p;
+            const uint32_t thr_k = thr;
+            thr = 0;
+            for (int bit = 15; bit >= 0; --bit) {
+                const uint32_t cand = thr | (1u << bit);
+                const uint32_t lim = std::max(cand, thr_k);
+                m = 0.f;
+                FOR_RUN(if (key >= lim) m += __expf((key_val(key) - xmax) * inv_t);)
+                m = wave_sum_f(m);
+                float* rm = red_m[bit & 1];     // two buffers: one barrier per step
+                if (lane == 0) rm[wave] = m;
+                __syncthreads();
+                float tot = 0.f;
+#pragma unroll
+                for (int w = 0; w < NT_WAVES; ++w) tot += rm[w];
+                if (tot >= need) thr = cand;
+            }
+            thr = std::min(std::max(thr, thr_k), bk - 1);      // (the maximum is kept whatever the sums gave)
+        }
+
+        // ---- min-p: the lowest key that passes, found among the keys up to the maximum's (which passes)
+        if (min_p > 0.f) {
+            const float bound = logf(min_p);
+            uint32_t lo = 0, hi = bk - 1;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if ((key_val(mid) - xmax) * inv_t >= bound) hi = mid; else lo = mid + 1;
+            }
+            thr = std::max(thr, lo);
+        }
+
+        // ---- weights: this thread's run, then an exclusive scan over the threads
+        float mine = 0.f;
+        FOR_RUN(if (key >= thr) mine += __expf((key_val(key) - xmax) * inv_t);)
+        float incl = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float v = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += v;
+        }
+        float excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 0.f;
+        if (lane == 63) red_w[wave] = incl;
+        __syncthreads();
+        float before = 0.f, total = 0.f;
+#pragma unroll
+        for (int w = 0; w < NT_WAVES; ++w) {
+            if (w == wave) before = total;
+            total += red_w[w];
+        }
+        const int ui = std::min(std::max(step0, 0), Tu - 1);
+        const float target = u[(long)ui * gridDim.x + b] * total;
+
+        // ---- the first kept slot whose inclusive prefix exceeds the target; the last kept slot
+        float c = before + excl;
+        int first = 0x7fffffff, last = -1;
+        FOR_RUN(if (key >= thr) {
+            c += __expf((key_val(key) - xmax) * inv_t);
+            last = p;
+            if (c > target && first == 0x7fffffff) first = p;
+        })
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            first = std::min(first, __shfl_xor(first, o, 64));
+            last = std::max(last, __shfl_xor(last, o, 64));
+        }
+        if (lane == 0) { red_min[wave] = first; red_max[wave] = last; }
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < NT_WAVES; ++w) {
+            first = std::min(first, red_min[w]);
+            last = std::max(last, red_max[w]);
+        }
+        pick = first != 0x7fffffff ? first : last;
+    }
+
+    // ---- the step's bookkeeping: row b's words, plain stores by one thread
+    if (tid == 0) {
+        int64_t tok = pick - row.lo;
+        const int eos = params ? params[PRM_EOS] : -1;
+        if (done) {
+            uint8_t d = done[b];
+            if (d) tok = params ? params[PRM_PAD] : 0;
+            if (eos >= 0 && tok == eos) d = 1;
+            done[b] = d;
+        }
+        tok_out[b] = tok;
+        if (tokens_out && step0 >= 0 && step0 < To) tokens_out[(long)b * To + step0] = tok;
+        if (step) step[b] = step0 + 1;
+        if (lens) lens[b] += 1;
+    }
+}
+
 // slots per thread: the row's V columns and up to 7 slots of alignment over 1024 threads, in 8s
 inline int nt_run(int V) { return (((V + 7 + NT_THREADS - 1) / NT_THREADS) + 7) / 8 * 8; }
 
@@ -282,6 +513,33 @@ DDL_API int ddl_next_token(const void* logits, int B, int V, const void* u, int 
         next_token_k<false><<<B, NT_THREADS, 0, st>>>((const bf16_t*)logits, V, R, (const float*)u, Tu, (const int*)params,
                                                       (int*)step, (uint8_t*)done, (int64_t*)tok_out,
                                                       (int64_t*)tokens_out, To, (int*)lens);
+    }
+    DDL_RETURN_LAUNCH();
+}
+
+// ddl_next_token with params int32 [n_params] (5, or 8: top_p, min_p, repetition_penalty as fp32 bits) and the
+// penalty's history: history int64 [B, Lh] (nullable), of which row b counts its first history_lens[b] (int32 [B],
+// clamped to 0 .. Lh; nullable: all Lh) entries, plus tokens_out[b, :step[b]] when both are given.  The penalty is
+// applied to rows that fit LDS (ddl_next_token_lds(V) != 0); for longer rows the caller penalises the logits.
+DDL_API int ddl_next_token_ex(const void* logits, int B, int V, const void* u, int Tu, const void* params, int n_params,
+                              const void* history, int Lh, const void* history_lens, void* step, void* done,
+                              void* tok_out, void* tokens_out, int To, void* lens, hipStream_t st) {
+    if (B < 1 || V < 1 || V > (1 << 30) || !logits || !tok_out || (u && Tu < 1) || (tokens_out && To < 1) ||
+        (params && n_params != PRM_SAMPLE + 1 && n_params != PRM_EX) || (history && Lh < 1))
+        return (int)hipErrorInvalidValue;
+    const int R = nt_run(V);
+    const long bytes = ddl_next_token_lds(V);
+    if (bytes) {
+        static const bool ok = hipFuncSetAttribute((const void*)next_token_ex_k<true>,
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, NT_MAX_LDS) == hipSuccess;
+        if (!ok) return (int)hipErrorInvalidValue;
+        next_token_ex_k<true><<<B, NT_THREADS, (size_t)bytes, st>>>(
+            (const bf16_t*)logits, V, R, (const float*)u, Tu, (const int*)params, n_params, (const int64_t*)history, Lh,
+            (const int*)history_lens, (int*)step, (uint8_t*)done, (int64_t*)tok_out, (int64_t*)tokens_out, To, (int*)lens);
+    } else {
+        next_token_ex_k<false><<<B, NT_THREADS, 0, st>>>(
+            (const bf16_t*)logits, V, R, (const float*)u, Tu, (const int*)params, n_params, (const int64_t*)history, Lh,
+            (const int*)history_lens, (int*)step, (uint8_t*)done, (int64_t*)tok_out, (int64_t*)tokens_out, To, (int*)lens);
     }
     DDL_RETURN_LAUNCH();
 }

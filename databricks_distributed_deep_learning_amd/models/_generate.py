@@ -10,15 +10,18 @@ from __future__ import annotations
 import torch
 
 from .. import ops
+from ..ops.decode import check_filters, penalise_logits, sampling_kept
 
 
-def check_sampling(max_new_tokens: int, do_sample: bool, temperature: float, top_k) -> None:
+def check_sampling(max_new_tokens: int, do_sample: bool, temperature: float, top_k, top_p=None, min_p=None,
+                   repetition_penalty=None) -> None:
     if max_new_tokens < 1:
         raise ValueError("max_new_tokens must be at least 1")
     if do_sample and not temperature > 0:
         raise ValueError("temperature must be positive")
     if top_k is not None and top_k < 1:
         raise ValueError("top_k must be at least 1")
+    check_filters(top_p, min_p, repetition_penalty)
 
 
 def compact_prompts(input_ids: torch.Tensor, attention_mask):
@@ -44,13 +47,26 @@ def compact_prompts(input_ids: torch.Tensor, attention_mask):
 
 
 def token_loop(logits, decode_step, max_new_tokens, do_sample, temperature, top_k, eos_token_id, pad_token_id,
-               generator) -> torch.Tensor:
+               generator, top_p=None, min_p=None, repetition_penalty=None, history=None,
+               history_lens=None) -> torch.Tensor:
     """From the prompt's next-token ``logits [B, vocab]``: choose a token, ``decode_step(tok)`` -> the next
-    logits, until ``max_new_tokens`` or every row has produced ``eos_token_id`` -> the new tokens ``[B, n]``."""
+    logits, until ``max_new_tokens`` or every row has produced ``eos_token_id`` -> the new tokens ``[B, n]``.
+    ``top_p`` / ``min_p`` / ``repetition_penalty`` as ``ops.next_token`` defines them (by value, ties kept), the
+    penalty over the prompt (``history [B, S0]``, ``history_lens``) and the tokens generated so far."""
     done = torch.zeros(logits.shape[0], dtype=torch.bool, device=logits.device)
     new = []
     for i in range(max_new_tokens):
-        if do_sample:
+        if repetition_penalty is not None and repetition_penalty != 1.0:
+            logits = penalise_logits(logits, repetition_penalty, history, history_lens,
+                                     torch.stack(new, 1) if new else None,
+                                     torch.full_like(done, len(new), dtype=torch.int32))
+        if do_sample and (top_p is not None or min_p is not None):
+            x = logits.float()
+            kept = sampling_kept(x, float(torch.tensor(1.0 / temperature, dtype=torch.float32)), top_k,
+                                 1.0 if top_p is None else top_p, 0.0 if min_p is None else min_p)
+            z = torch.where(kept, x / temperature, torch.full_like(x, float("-inf")))
+            tok = torch.multinomial(torch.softmax(z, -1), 1, generator=generator).squeeze(1)
+        elif do_sample:
             z = logits.float() / temperature
             if top_k is not None and top_k < z.shape[-1]:
                 kth = z.topk(top_k, -1).values[:, -1:]
@@ -75,15 +91,19 @@ def use_graph_for(weight: torch.Tensor) -> bool:
 
 
 def session_loop(sess, consume_prompt, batch, device, max_new_tokens, do_sample, temperature, top_k, eos_token_id,
-                 pad_token_id, generator) -> torch.Tensor:
+                 pad_token_id, generator, top_p=None, min_p=None, repetition_penalty=None, history=None,
+                 history_lens=None) -> torch.Tensor:
     """``token_loop`` on a decode session: ``consume_prompt(sess.cache)`` -> the prompt's logits, the first
-    token by the step's own kernel, then one ``advance`` per token -> the new tokens ``[B, n]``."""
+    token by the step's own kernel, then one ``advance`` per token -> the new tokens ``[B, n]``.  The three
+    further settings need a session made for them (``session_for(..., ext=True)``), which also takes the
+    prompts (``history [B, S0]``, ``history_lens``) the penalty counts."""
     u = None
     if do_sample:
         u = torch.rand(max_new_tokens, batch, generator=generator,
                        device=device if generator is None else generator.device).to(device)
     sess.begin(ops.next_token_params(1.0 / temperature if do_sample else 1.0, top_k, eos_token_id, pad_token_id,
-                                     do_sample, device), u)
+                                     do_sample, device, top_p=top_p, min_p=min_p,
+                                     repetition_penalty=repetition_penalty), u, history, history_lens)
     sess.first_token(consume_prompt(sess.cache))
     n = 1
     while n < max_new_tokens:

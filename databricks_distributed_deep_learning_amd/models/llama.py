@@ -383,7 +383,8 @@ class LlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, max_new_tokens: int = 20, do_sample: bool = False,
                  temperature: float = 1.0, top_k=None, eos_token_id=None, pad_token_id=None, generator=None,
-                 use_graph: bool = False, prefix: LlamaKVCache = None):
+                 use_graph: bool = False, prefix: LlamaKVCache = None, top_p=None, min_p=None,
+                 repetition_penalty=None):
         """Greedy (argmax) or sampled (temperature, then top-k, then multinomial) continuation of
         ``input_ids [B, S_in]`` -> ``[B, S_in + n_new]``: ``GPT2LMHeadModel.generate``'s contract.  Each row
         as given, then its generated tokens, with ``pad_token_id`` (default ``eos_token_id``) after the first
@@ -402,12 +403,18 @@ class LlamaForCausalLM(nn.Module):
         ``torch.rand(max_new_tokens, B, generator=generator)`` drawn before the loop.  The eos check syncs
         only every 16 steps; the result is trimmed to the length ``use_graph=False`` returns.
 
+        ``top_p`` (nucleus), ``min_p`` and ``repetition_penalty`` are ``ops.next_token``'s, applied in HF's
+        order (penalty, temperature, top-k, top-p, min-p) and defined by value, so ties at a cut are kept;
+        the penalty counts a row's prompt and its generated tokens (not the tokens of a ``prefix`` cache), and
+        applies to greedy too.  Left at None, every path gives the tokens it gave without them.
+
         ``prefix``: a ``LlamaKVCache`` (of batch B, or of batch 1 and shared by every row) that already holds
         the tokens before ``input_ids``, e.g. a system prompt prefilled once: it is copied into this call's
         own cache (the session's, under ``use_graph``), never modified, and the prompt is consumed by
         ``extend`` on top of it, so row b's prompt starts at rotary position ``prefix.lens[b]``."""
         B, S_in = input_ids.shape
-        G.check_sampling(max_new_tokens, do_sample, temperature, top_k)
+        G.check_sampling(max_new_tokens, do_sample, temperature, top_k, top_p, min_p, repetition_penalty)
+        ext = top_p is not None or min_p is not None or repetition_penalty is not None
         n_pos = self.config.max_position_embeddings
         P0 = 0 if prefix is None else prefix.max_len
         if P0 + S_in + max_new_tokens > n_pos:
@@ -424,15 +431,17 @@ class LlamaForCausalLM(nn.Module):
             if use_graph:
                 from ._decode_graph import round_capacity, session_for
                 sess = session_for(self, B, round_capacity(need, n_pos),
-                                   G.use_graph_for(self.embed_tokens.weight))
+                                   G.use_graph_for(self.embed_tokens.weight), ext)
                 new = G.session_loop(sess, lambda cache: self._consume_prompt(ids, cnt, cache, prefix), B, dev,
                                      max_new_tokens, do_sample, temperature, top_k, eos_token_id, pad_token_id,
-                                     generator)
+                                     generator, top_p, min_p, repetition_penalty, ids if ext else None,
+                                     cnt if ext else None)
             else:
                 cache = LlamaKVCache.allocate(self, B, need, dev)
                 new = G.token_loop(self._consume_prompt(ids, cnt, cache, prefix),
                                    lambda tok: self.decode_step(tok, cache), max_new_tokens, do_sample,
-                                   temperature, top_k, eos_token_id, pad_token_id, generator)
+                                   temperature, top_k, eos_token_id, pad_token_id, generator, top_p, min_p,
+                                   repetition_penalty, ids, cnt)
         finally:
             self.train(was_training)
         return torch.cat([input_ids, new.to(input_ids.dtype)], 1)

@@ -13,6 +13,7 @@ from ._lib import I, L, P
 _lib.register({
     "ddl_next_token_lds": [I],
     "ddl_next_token": [P, I, I, P, I, P, P, P, P, P, I, P],
+    "ddl_next_token_ex": [P, I, I, P, I, P, I, P, I, P, P, P, P, P, I, P],
     "ddl_decode_embed": [P, P, P, P, P, I, I, I, I],
 })
 
@@ -36,5 +37,16 @@ def next_token(logits, u, params, step, done, out, tokens_out, lens):
     B, V = logits.shape
     _lib.call("ddl_next_token", logits.data_ptr(), B, V, _lib.p(u), 0 if u is None else u.shape[0], _lib.p(params),
               _lib.p(step), _lib.p(done), out.data_ptr(), _lib.p(tokens_out),
+              0 if tokens_out is None else tokens_out.shape[1], _lib.p(lens))
+    return out
+
+
+def next_token_ex(logits, u, params, history, history_lens, step, done, out, tokens_out, lens):
+    """``params`` int32 ``[5]`` or ``[8]``; the penalty counts ``history`` / ``tokens_out[:, :step]`` on rows that
+    fit LDS (``row_in_lds``) -- a longer row's logits come here already penalised."""
+    B, V = logits.shape
+    _lib.call("ddl_next_token_ex", logits.data_ptr(), B, V, _lib.p(u), 0 if u is None else u.shape[0],
+              params.data_ptr(), params.shape[0], _lib.p(history), 0 if history is None else history.shape[1],
+              _lib.p(history_lens), _lib.p(step), _lib.p(done), out.data_ptr(), _lib.p(tokens_out),
               0 if tokens_out is None else tokens_out.shape[1], _lib.p(lens))
     return out
