@@ -138,19 +138,41 @@ def attention(qkv: torch.Tensor, num_heads: int, mask: Optional[torch.Tensor] = 
 # to the new key, and the new K / V rows are stored to cache[b, :, n].  lens is NOT changed: every layer
 # of a decode step shares it and the caller adds 1 once per step.  max_len is the host's upper bound on
 # n + 1 (it sizes the launch); positions past n never reach the output, whatever they hold.
-def _decode_guard(qkv_new, cache_k, cache_v, lens, max_len):
-    if any(t.requires_grad for t in (qkv_new, cache_k, cache_v)):
-        raise RuntimeError("attention_decode has no autograd: call it under torch.no_grad() on detached tensors")
-    C = cache_k.shape[2]
-    if max_len > C:
-        raise ValueError(f"max_len {max_len} exceeds the cache capacity {C}")
+def _no_autograd(name, *tensors):
+    if any(t.requires_grad for t in tensors):
+        raise RuntimeError(f"{name} has no autograd: call it under torch.no_grad() on detached tensors")
+
+
+def _check_lens(B, lens, new_lens=None):
+    for name, t in (("lens", lens), ("new_lens", new_lens)):
+        if t is not None and (t.dtype != torch.int32 or t.shape != (B,) or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous int32 [B] tensor")
+
+
+def _decode_bounds(cache_k, max_len):
+    """``max_len`` bounds ``lens + 1`` and must fit the cache."""
+    if max_len > cache_k.shape[2]:
+        raise ValueError(f"max_len {max_len} exceeds the cache capacity {cache_k.shape[2]}")
     if max_len < 1:
         raise ValueError("max_len counts the new token: at least 1")
 
 
+def _extend_bounds(cache_k, max_len, T):
+    """``max_len`` bounds ``lens``; the chunk's ``T`` tokens come on top and must fit the cache."""
+    if max_len < 0:
+        raise ValueError("max_len bounds lens: at least 0")
+    if max_len + T > cache_k.shape[2]:
+        raise ValueError(f"max_len {max_len} + the chunk's {T} tokens exceeds the cache capacity {cache_k.shape[2]}")
+
+
+def _decode_guard(qkv_new, cache_k, cache_v, max_len):
+    _no_autograd("attention_decode", qkv_new, cache_k, cache_v)
+    _decode_bounds(cache_k, max_len)
+
+
 def attention_decode_reference(qkv_new: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
                                lens: torch.Tensor, num_heads: int, max_len: int) -> torch.Tensor:
-    _decode_guard(qkv_new, cache_k, cache_v, lens, max_len)
+    _decode_guard(qkv_new, cache_k, cache_v, max_len)
     B, three_hd = qkv_new.shape
     D = three_hd // (3 * num_heads)
     q, k, v = qkv_new.view(B, 3, num_heads, D).unbind(1)
@@ -172,12 +194,12 @@ def attention_decode_reference(qkv_new: torch.Tensor, cache_k: torch.Tensor, cac
 def attention_decode(qkv_new: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor, lens: torch.Tensor,
                      num_heads: int, max_len: int) -> torch.Tensor:
     """Single-query attention over the cache, with the append; returns ``[B, H·D]``."""
-    _decode_guard(qkv_new, cache_k, cache_v, lens, max_len)
+    _decode_guard(qkv_new, cache_k, cache_v, max_len)
     if (_lib.use_native(qkv_new, cache_k, cache_v, lens) and qkv_new.dtype == torch.bfloat16
             and cache_k.dtype == torch.bfloat16 and cache_v.dtype == torch.bfloat16
             and qkv_new.shape[1] == 3 * 64 * num_heads):
-        from . import _native_attn_decode
-        return _native_attn_decode.attention_decode(qkv_new, cache_k, cache_v, lens, num_heads, max_len)
+        from . import _native_attn_cache
+        return _native_attn_cache.attention_decode(qkv_new, cache_k, cache_v, lens, num_heads, max_len)
     return attention_decode_reference(qkv_new, cache_k, cache_v, lens, num_heads, max_len)
 
 
@@ -192,14 +214,13 @@ def kv_cache_fill_reference(qkv: torch.Tensor, cache_k: torch.Tensor, cache_v: t
 def kv_cache_fill(qkv: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor, num_heads: int) -> None:
     """After a prefill: the K and V thirds of the packed ``[B, S, 3·H·D]`` projection into cache positions
     0..S-1 (rows past a sequence's own length too: they are dead by ``lens``)."""
-    if any(t.requires_grad for t in (qkv, cache_k, cache_v)):
-        raise RuntimeError("kv_cache_fill has no autograd: call it under torch.no_grad() on detached tensors")
+    _no_autograd("kv_cache_fill", qkv, cache_k, cache_v)
     if qkv.shape[1] > cache_k.shape[2]:
         raise ValueError(f"sequence length {qkv.shape[1]} exceeds the cache capacity {cache_k.shape[2]}")
     if (_lib.use_native(qkv, cache_k, cache_v) and qkv.dtype == torch.bfloat16 and cache_k.dtype == torch.bfloat16
             and cache_v.dtype == torch.bfloat16 and qkv.shape[2] == 3 * 64 * num_heads):
-        from . import _native_attn_decode
-        return _native_attn_decode.kv_cache_fill(qkv, cache_k, cache_v, num_heads)
+        from . import _native_attn_cache
+        return _native_attn_cache.kv_cache_fill(qkv, cache_k, cache_v, num_heads)
     return kv_cache_fill_reference(qkv, cache_k, cache_v, num_heads)
 
 
@@ -214,15 +235,10 @@ def kv_cache_fill(qkv: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tenso
 # lens is NOT changed (every layer shares it; the caller adds new_lens once).  max_len is the host's
 # upper bound on lens; max_len + T must fit the capacity.
 def _extend_guard(qkv_new, cache_k, cache_v, max_len):
-    if any(t.requires_grad for t in (qkv_new, cache_k, cache_v)):
-        raise RuntimeError("attention_extend has no autograd: call it under torch.no_grad() on detached tensors")
+    _no_autograd("attention_extend", qkv_new, cache_k, cache_v)
     if qkv_new.dim() != 3 or qkv_new.shape[1] < 1:
         raise ValueError(f"qkv_new must be [B, T >= 1, 3·H·D], got {tuple(qkv_new.shape)}")
-    C, T = cache_k.shape[2], qkv_new.shape[1]
-    if max_len < 0:
-        raise ValueError("max_len bounds lens: at least 0")
-    if max_len + T > C:
-        raise ValueError(f"max_len {max_len} + the chunk's {T} tokens exceeds the cache capacity {C}")
+    _extend_bounds(cache_k, max_len, qkv_new.shape[1])
 
 
 def attention_extend_reference(qkv_new: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
@@ -264,8 +280,8 @@ def attention_extend(qkv_new: torch.Tensor, cache_k: torch.Tensor, cache_v: torc
     if (_lib.use_native(qkv_new, cache_k, cache_v, lens, new_lens) and qkv_new.dtype == torch.bfloat16
             and cache_k.dtype == torch.bfloat16 and cache_v.dtype == torch.bfloat16
             and qkv_new.shape[2] == 3 * 64 * num_heads):
-        from . import _native_attn_extend
-        return _native_attn_extend.attention_extend(qkv_new, cache_k, cache_v, lens, num_heads, max_len, new_lens)
+        from . import _native_attn_cache
+        return _native_attn_cache.attention_extend(qkv_new, cache_k, cache_v, lens, num_heads, max_len, new_lens)
     return attention_extend_reference(qkv_new, cache_k, cache_v, lens, num_heads, max_len, new_lens)
 
 
@@ -293,8 +309,7 @@ def _check_gqa_cache(cache_k, cache_v, B, num_kv_heads, D):
 
 
 def _decode_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len):
-    if any(t.requires_grad for t in (qkv_new, table, cache_k, cache_v)):
-        raise RuntimeError("attention_decode_gqa has no autograd: call it under torch.no_grad() on detached tensors")
+    _no_autograd("attention_decode_gqa", qkv_new, table, cache_k, cache_v)
     _gqa_heads(num_heads, num_kv_heads)
     W = num_heads + 2 * num_kv_heads
     if qkv_new.dim() != 2 or qkv_new.shape[1] % W or (qkv_new.shape[1] // W) % 2:
@@ -303,13 +318,8 @@ def _decode_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_
     _check_gqa_cache(cache_k, cache_v, B, num_kv_heads, D)
     if table.dim() != 2 or table.shape[1] != D:
         raise ValueError(f"table must be [n_positions, {D}], got {tuple(table.shape)}")
-    if lens.dtype != torch.int32 or lens.shape != (B,) or not lens.is_contiguous():
-        raise ValueError("lens must be a contiguous int32 [B] tensor")
-    C = cache_k.shape[2]
-    if max_len > C:
-        raise ValueError(f"max_len {max_len} exceeds the cache capacity {C}")
-    if max_len < 1:
-        raise ValueError("max_len counts the new token: at least 1")
+    _check_lens(B, lens)
+    _decode_bounds(cache_k, max_len)
     if max_len > table.shape[0]:
         raise ValueError(f"max_len {max_len} exceeds the rotary table's {table.shape[0]} positions")
     return D
@@ -356,15 +366,14 @@ def attention_decode_gqa(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: to
     if (_lib.use_native(qkv_new, table, cache_k, cache_v, lens) and qkv_new.dtype == torch.bfloat16
             and cache_k.dtype == torch.bfloat16 and cache_v.dtype == torch.bfloat16
             and table.dtype == torch.float32 and D == 64):
-        from . import _native_attn_decode_gqa as N
+        from . import _native_attn_cache as N
         if N.supported(num_heads, num_kv_heads):
             return N.attention_decode_gqa(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len)
     return attention_decode_gqa_reference(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len)
 
 
 def _fill_gqa_guard(packed, cache_k, cache_v, num_heads, num_kv_heads):
-    if any(t.requires_grad for t in (packed, cache_k, cache_v)):
-        raise RuntimeError("kv_cache_fill_gqa has no autograd: call it under torch.no_grad() on detached tensors")
+    _no_autograd("kv_cache_fill_gqa", packed, cache_k, cache_v)
     _gqa_heads(num_heads, num_kv_heads)
     if packed.dim() != 3 or packed.shape[2] % (3 * num_heads):
         raise ValueError(f"packed must be rope_qkv's [B, S, 3·H·D], got {tuple(packed.shape)}")
@@ -393,7 +402,7 @@ def kv_cache_fill_gqa(packed: torch.Tensor, cache_k: torch.Tensor, cache_v: torc
     D = _fill_gqa_guard(packed, cache_k, cache_v, num_heads, num_kv_heads)
     if (_lib.use_native(packed, cache_k, cache_v) and packed.dtype == torch.bfloat16
             and cache_k.dtype == torch.bfloat16 and cache_v.dtype == torch.bfloat16 and D == 64):
-        from . import _native_attn_decode_gqa as N
+        from . import _native_attn_cache as N
         return N.kv_cache_fill_gqa(packed, cache_k, cache_v, num_heads, num_kv_heads)
     return kv_cache_fill_gqa_reference(packed, cache_k, cache_v, num_heads, num_kv_heads)
 
@@ -410,8 +419,7 @@ def kv_cache_fill_gqa(packed: torch.Tensor, cache_k: torch.Tensor, cache_v: torc
 # pass a row with no real token hands it t = 1, as for attention_extend.)  lens and new_lens are NOT changed;
 # max_len is the host's upper bound on lens, and max_len + T must fit both the cache and the table.
 def _extend_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len, new_lens):
-    if any(t.requires_grad for t in (qkv_new, table, cache_k, cache_v)):
-        raise RuntimeError("attention_extend_gqa has no autograd: call it under torch.no_grad() on detached tensors")
+    _no_autograd("attention_extend_gqa", qkv_new, table, cache_k, cache_v)
     _gqa_heads(num_heads, num_kv_heads)
     W = num_heads + 2 * num_kv_heads
     if qkv_new.dim() != 3 or qkv_new.shape[1] < 1 or qkv_new.shape[2] % W or (qkv_new.shape[2] // W) % 2:
@@ -420,14 +428,8 @@ def _extend_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_
     _check_gqa_cache(cache_k, cache_v, B, num_kv_heads, D)
     if table.dim() != 2 or table.shape[1] != D:
         raise ValueError(f"table must be [n_positions, {D}], got {tuple(table.shape)}")
-    for name, t in (("lens", lens), ("new_lens", new_lens)):
-        if t is not None and (t.dtype != torch.int32 or t.shape != (B,) or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous int32 [B] tensor")
-    C = cache_k.shape[2]
-    if max_len < 0:
-        raise ValueError("max_len bounds lens: at least 0")
-    if max_len + T > C:
-        raise ValueError(f"max_len {max_len} + the chunk's {T} tokens exceeds the cache capacity {C}")
+    _check_lens(B, lens, new_lens)
+    _extend_bounds(cache_k, max_len, T)
     if max_len + T > table.shape[0]:
         raise ValueError(f"max_len {max_len} + the chunk's {T} tokens exceeds the rotary table's {table.shape[0]} "
                          f"positions")
@@ -489,10 +491,9 @@ def attention_extend_gqa(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: to
     if (_lib.use_native(qkv_new, table, cache_k, cache_v, lens, new_lens) and qkv_new.dtype == torch.bfloat16
             and cache_k.dtype == torch.bfloat16 and cache_v.dtype == torch.bfloat16
             and table.dtype == torch.float32 and D == 64):
-        from . import _native_attn_decode_gqa as N
+        from . import _native_attn_cache as N
         if N.supported(num_heads, num_kv_heads):
-            from . import _native_attn_extend_gqa
-            return _native_attn_extend_gqa.attention_extend_gqa(qkv_new, table, cache_k, cache_v, lens, num_heads,
-                                                                num_kv_heads, max_len, new_lens)
+            return N.attention_extend_gqa(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len,
+                                          new_lens)
     return attention_extend_gqa_reference(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len,
                                           new_lens)

@@ -106,7 +106,7 @@ def test_parity_random(tight):
 @pytest.mark.parametrize("b,h", [(8, 16), (16, 16)], ids=["bh128-2splits", "bh256-1split"])
 def test_parity_other_geometries(b, h):
     """Long splits (several rounds each) and the direct-output path at a long length."""
-    from databricks_distributed_deep_learning_amd.ops import _native_attn_decode as ND
+    from databricks_distributed_deep_learning_amd.ops import _native_attn_cache as ND
     dev = gpu_device()
     lens = [(LENGTHS[(3 * i + 1) % len(LENGTHS)]) for i in range(b)]
     lens[0], lens[-1] = 1023, 0
@@ -119,7 +119,7 @@ def test_parity_other_geometries(b, h):
 
 
 def test_plan_is_what_the_docstring_says():
-    from databricks_distributed_deep_learning_amd.ops import _native_attn_decode as ND
+    from databricks_distributed_deep_learning_amd.ops import _native_attn_cache as ND
     gpu_device()
     if torch.cuda.get_device_properties(0).multi_processor_count != 256:
         return      # the listed split edges are those of a 256-CU part
@@ -217,7 +217,7 @@ def test_append(lens, tight):
 
 
 def test_repeatable():
-    from databricks_distributed_deep_learning_amd.ops import _native_attn_decode as ND
+    from databricks_distributed_deep_learning_amd.ops import _native_attn_cache as ND
     dev = gpu_device()
     assert ND.plan(B, H, C)[0] > 1
     qkv, ck, cv, lt = make_random([1000, 700], dev, 23)

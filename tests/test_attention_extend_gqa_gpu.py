@@ -1,5 +1,5 @@
 """Grouped-query chunk attention over a rotated KV cache with the chunk's rotation and the append (GPU only;
-csrc/kernels/attn_extend_gqa.hip), in the form of tests/test_attention_extend_gpu.py.
+the rotary instances of csrc/kernels/attn_extend.hip), in the form of tests/test_attention_extend_gpu.py.
 
 Every case has two batch rows of DIFFERENT cached lengths n (B = 2, C = 384).  (H, Hkv) = (4, 2) runs the full
 lists; (1, 1), (3, 1), (4, 1) and (8, 1) -- the other group sizes with an instance -- run reduced ones.
@@ -143,7 +143,7 @@ def _check_case(fails, label, hh, qkv, table, ck, cv, ns, ts, max_len, ragged):
 
 
 def test_routes_to_the_kernel():
-    from databricks_distributed_deep_learning_amd.ops import _native_attn_extend_gqa as N
+    from databricks_distributed_deep_learning_amd.ops import _native_attn_cache as N
     assert all(N.supported(*hh) for hh in [MAIN] + OTHERS) and not N.supported(5, 1) and not N.supported(6, 4)
     assert [N.tile(T, 4, 2) for T in (16, 17, 32, 33)] == [16, 32, 32, 64]
     assert [N.tile(T, 3, 1) for T in (16, 17, 33)] == [16, 32, 32] and N.tile(129, 8, 1) == 16
