@@ -4,7 +4,7 @@ and the decode attention against what the library could compose before it.
 
     python benchmarks/llama_generate_bench.py [--model smollm_135m] [--prompt 128] [--new 128]
                                               [--batches 1,8,16] [--reps 3] [--skip-e2e] [--skip-recompute]
-                                              [--skip-kernels]
+                                              [--skip-kernels] [--skip-d128]
 
 End to end (bf16, random weights, greedy, no eos): ``generate`` (prefill + cached decode steps), the same with
 ``use_graph=True`` (the decode step captured once and replayed; the capture is timed once, apart) and the
@@ -22,6 +22,12 @@ totalling >= 512 MB, more than the 256 MB last-level cache, so the rows come fro
     appends).
 Bytes are what each algorithm must read: 2 (n + 1) 128 B per (batch, KV head) for the GQA kernel, per (batch,
 query head) for the other two.
+
+Head dim 128 (``--skip-d128`` leaves it out), same method: (H, Hkv) = (32, 8) and (32, 32), B = 1 and 16, 1023
+and 8191 cached keys; ``ops.attention_decode_gqa`` against ``attention_decode_gqa_reference`` on the same tensors
+(what these shapes ran before the D = 128 kernel) and masked SDPA over the H-head cache; 2 (n + 1) 256 B per
+(batch, KV head).  Then one end-to-end line: ``llama3_8b(num_hidden_layers=4)`` at B = 16, ``generate`` eager
+and with ``use_graph=True``.
 """
 import argparse
 import json
@@ -91,6 +97,85 @@ def bench_attention(dev):
                           "masked_sdpa_us": round(t_s, 2), "masked_sdpa_GBps": round(nbx / t_s / 1e3, 1),
                           "no_slower_than_composition": bool(t_o <= t_c)}), flush=True)
         del small, big
+
+
+def d128_bytes(B, Hkv, n):
+    """What the D = 128 decode must read: 2 (n + 1) 256 B per (batch, KV head)."""
+    return 2 * (n + 1) * 256 * B * Hkv
+
+
+def bench_attention_d128(dev):
+    """Head dim 128 per call, same method as above: the kernel, ``attention_decode_gqa_reference`` on the same
+    tensors (what these shapes ran before the kernel) and masked SDPA over a cache expanded to H heads."""
+    import torch
+    import torch.nn.functional as F
+    from databricks_distributed_deep_learning_amd import ops
+    from databricks_distributed_deep_learning_amd.ops.attention import attention_decode_gqa_reference
+    D = 128
+    for n in (1023, 8191):
+        C = n + 1
+        table = ops.rope_table(C, 5e5, D, dev)
+        for H, Hkv in ((32, 8), (32, 32)):
+            for B in (1, 16):
+                lens = torch.full((B,), n, dtype=torch.int32, device=dev)
+                L = min(256, -(-ROTATE_BYTES // (2 * B * Hkv * C * D * 2)))
+                Lx = min(256, -(-ROTATE_BYTES // (2 * B * H * C * D * 2)))
+                small = torch.randn(L, 2, B, Hkv, C, D, device=dev).bfloat16()
+                big = small if H == Hkv else torch.randn(Lx, 2, B, H, C, D, device=dev).bfloat16()
+                proj = torch.randn(B, (H + 2 * Hkv) * D, device=dev).bfloat16()
+                q = torch.randn(B, H, 1, D, device=dev).bfloat16()
+                keep = (torch.arange(C, device=dev)[None, :] <= lens[:, None]).view(B, 1, 1, C)
+
+                def ours(i):
+                    ops.attention_decode_gqa(proj, table, small[i % L, 0], small[i % L, 1], lens, H, Hkv, n + 1)
+
+                def reference(i):
+                    attention_decode_gqa_reference(proj, table, small[i % L, 0], small[i % L, 1], lens, H, Hkv, n + 1)
+
+                def sdpa(i):
+                    F.scaled_dot_product_attention(q, big[i % Lx, 0], big[i % Lx, 1], attn_mask=keep)
+
+                slow = 20 if n > 4096 else 100
+                with torch.no_grad():
+                    t_o, t_r, t_s = _best(ours, 400), _best(reference, slow), _best(sdpa, slow)
+                nb, nbx = d128_bytes(B, Hkv, n), d128_bytes(B, H, n)
+                print(json.dumps({"kernel": "attention_decode_gqa_d128", "B": B, "H": H, "Hkv": Hkv, "G": H // Hkv,
+                                  "n": n, "copies": L, "us": round(t_o, 2), "GBps": round(nb / t_o / 1e3, 1),
+                                  "share_of_stream": round(nb / t_o / 1e6 / STREAM_TBS, 4),
+                                  "reference_us": round(t_r, 2), "reference_GBps": round(nb / t_r / 1e3, 1),
+                                  "masked_sdpa_us": round(t_s, 2), "masked_sdpa_GBps": round(nbx / t_s / 1e3, 1),
+                                  "faster_than_reference": bool(t_o < t_r)}), flush=True)
+                del small, big
+
+
+def bench_e2e_d128(dev, args):
+    """``llama3_8b(num_hidden_layers=4)``: ``generate`` eager and graph-replayed, tokens/s."""
+    import torch
+    from databricks_distributed_deep_learning_amd.models import cast_params, llama3_8b
+    torch.manual_seed(0)
+    with torch.device(dev):
+        model = llama3_8b(num_hidden_layers=4).eval()
+    model = model.to(dev)
+    cast_params(model, torch.bfloat16)
+    B = 16
+    ids = torch.randint(0, model.config.vocab_size, (B, args.prompt), device=dev)
+    arms = {"cached": lambda: model.generate(ids, max_new_tokens=args.new),
+            "graph": lambda: model.generate(ids, max_new_tokens=args.new, use_graph=True)}
+    outs, times = {}, {name: [] for name in arms}
+    for rep in range(args.reps + 1):        # (the first round warms up and captures)
+        for name, fn in arms.items():
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            outs[name] = fn()
+            torch.cuda.synchronize()
+            if rep:
+                times[name].append(time.perf_counter() - t)
+    c, g = min(times["cached"]), min(times["graph"])
+    print(json.dumps({"e2e": "llama3_8b(num_hidden_layers=4)", "B": B, "prompt": args.prompt, "new": args.new,
+                      "cached_tokens_per_s": round(B * args.new / c, 1), "graph_tokens_per_s": round(B * args.new / g, 1),
+                      "graph_speedup_over_cached": round(c / g, 2), "graph_captures": model.decode_session.captures,
+                      "graph_token_agreement_with_cached": round((outs["cached"] == outs["graph"]).float().mean().item(), 4)}),
+          flush=True)
 
 
 def bench_e2e(dev, args):
@@ -171,6 +256,7 @@ def main() -> int:
     ap.add_argument("--skip-e2e", action="store_true")
     ap.add_argument("--skip-kernels", action="store_true")
     ap.add_argument("--skip-recompute", action="store_true", help="end to end: the cached and graph arms only")
+    ap.add_argument("--skip-d128", action="store_true", help="no head-dim-128 section (per call and llama3_8b)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -180,6 +266,9 @@ def main() -> int:
         bench_e2e(dev, args)
     if not args.skip_kernels:
         bench_attention(dev)
+    if not args.skip_d128:
+        bench_attention_d128(dev)
+        bench_e2e_d128(dev, args)
     return 0
 
 

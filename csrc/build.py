@@ -59,6 +59,11 @@ def needs(src, obj, hdr_mtime):
 _VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 EXTRA = {"gemm_big.hip": _VGPR_FORM, "conv3x3.hip": _VGPR_FORM, "skinny_gemm.hip": _VGPR_FORM,
          "stream_gemm.hip": _VGPR_FORM, "gemm_duo.hip": _VGPR_FORM, "conv3_bwd.hip": _VGPR_FORM}
+# No packed-fp32 VALU (v_pk_add / mul / fma_f32) in sources added from here on: their fp32 math is the scalar
+# forms the source spells, whatever pairs the vectoriser would find.  (Older sources keep the flags their
+# committed results were measured with.)
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA["attn_decode_d128.hip"] = _NO_PK_F32
 
 
 # Sources whose code decides which GEMM kernel runs fastest for a shape: their hash keys the committed

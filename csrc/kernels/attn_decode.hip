@@ -34,42 +34,16 @@
 // them in split order: no float atomics, no in-launch hand-off; nsplit = 1 writes out directly.  Positions
 // past n are never loaded (selects, not multiplies, keep them out), so whatever bit patterns the unwritten
 // part of the cache holds cannot reach the output.
-#include "ddl_common.h"
+//
+// The split plan and the 16-byte piece helpers are attn_decode.h's, shared with the head-dim-128 rotary decode
+// (attn_decode_d128.hip).
+#include "attn_decode.h"
 
 namespace {
 
 constexpr int DEC_D = 64;
-constexpr int DEC_NT = 256;                 // threads per workgroup
 constexpr int DEC_GRPS = DEC_NT / 8;        // key groups per workgroup
-constexpr int DEC_MAX_SPLIT = 16;           // ddl_attn_decode
-constexpr int DEC_MAX_SPLIT_GQA = 32;       // ddl_attn_decode_gqa
-constexpr int DEC_MIN_CHUNK = 64;           // positions per split, at least (and a multiple of DEC_GRPS)
-constexpr float LOG2E = 1.4426950408889634f;
-
-struct DecPlan {
-    int nsplit, chunk;
-};
-
-// From max_len alone: enough splits (max_split at most) that B Hkv nsplit covers the chip, each at least
-// DEC_MIN_CHUNK positions, chunk a multiple of DEC_GRPS.
-inline DecPlan dec_plan(int B, int Hkv, int max_len, int max_split) {
-    const int bh = std::max(1, B * Hkv);
-    int want = std::min(max_split, (num_cus() + bh - 1) / bh);
-    want = std::max(1, std::min(want, (max_len + DEC_MIN_CHUNK - 1) / DEC_MIN_CHUNK));
-    int chunk = (max_len + want - 1) / want;
-    chunk = (chunk + DEC_GRPS - 1) / DEC_GRPS * DEC_GRPS;
-    return {(max_len + chunk - 1) / chunk, chunk};
-}
-
-__device__ __forceinline__ void unpack8(const uint4& u, float* v) {
-    v[0] = lo_f(u.x); v[1] = hi_f(u.x); v[2] = lo_f(u.y); v[3] = hi_f(u.y);
-    v[4] = lo_f(u.z); v[5] = hi_f(u.z); v[6] = lo_f(u.w); v[7] = hi_f(u.w);
-}
-__device__ __forceinline__ uint4 pack8(const float* v) {
-    return make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
-}
-__device__ __forceinline__ uint4 ld16(const bf16_t* p) { return *reinterpret_cast<const uint4*>(p); }
-__device__ __forceinline__ void st16(bf16_t* p, const uint4& u) { *reinterpret_cast<uint4*>(p) = u; }
+static_assert(DEC_PLAN_ALIGN % DEC_GRPS == 0, "a split's chunk must be whole rounds of groups");
 
 // sum over the 8 lanes of a group (lanes 8 g .. 8 g + 7): xor 1, 2 inside the quad, then xor 4
 __device__ __forceinline__ float group8_sum(float v) {
@@ -284,12 +258,6 @@ __global__ __launch_bounds__(256) void kv_cache_fill_k(const bf16_t* __restrict_
     const long HD = (long)Hkv * G * DEC_D;
     const uint4 u = ld16(packed + (b * S + s) * 3 * HD + (1 + kv) * HD + (long)hkv * G * DEC_D + sub * 8);
     st16((kv ? vcache : kcache) + ((b * Hkv + hkv) * C + s) * DEC_D + sub * 8, u);
-}
-
-inline bool gqa_group_ok(int H, int Hkv) {
-    if (Hkv < 1 || H < Hkv || H % Hkv) return false;
-    const int G = H / Hkv;
-    return G == 1 || G == 2 || G == 3 || G == 4 || G == 8;
 }
 
 // the decode launch and, with more than one split, the merge

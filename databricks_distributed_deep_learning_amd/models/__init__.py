@@ -1,5 +1,5 @@
 """Model zoo (N11): ResNet-18/34/50/101/152, BERT-base/large (+ a tiny test size), ViT-B/16,
-GPT-2 small/medium/large (+ a tiny test size), Llama-family SmolLM-135M/360M/1.7B (+ a tiny test size)."""
+GPT-2 small/medium/large (+ a tiny test size), Llama-family SmolLM-135M/360M/1.7B, Llama-2-7B and Llama-3-8B (+ a tiny test size)."""
 from __future__ import annotations
 
 import torch.nn as nn
@@ -11,6 +11,7 @@ from .vit import ViTConfig, ViTForImageClassification, vit_b16  # noqa: F401
 from .gpt2 import GPT2Config, GPT2LMHeadModel, KVCache, gpt2, gpt2_medium, gpt2_large, gpt2_tiny  # noqa: F401
 from .llama import LlamaKVCache  # noqa: F401
 from .llama import LlamaConfig, LlamaForCausalLM, llama_tiny, smollm_135m, smollm_360m, smollm_1p7b  # noqa: F401
+from .llama import llama2_7b, llama3_8b  # noqa: F401
 from .layers import cast_params, convert_sync_batchnorm  # noqa: F401
 
 _REGISTRY = {
@@ -22,6 +23,7 @@ _REGISTRY = {
     "vit_b16": vit_b16,
     "gpt2": gpt2, "gpt2_medium": gpt2_medium, "gpt2_large": gpt2_large, "gpt2_tiny": gpt2_tiny,
     "llama_tiny": llama_tiny, "smollm_135m": smollm_135m, "smollm_360m": smollm_360m, "smollm_1p7b": smollm_1p7b,
+    "llama2_7b": llama2_7b, "llama3_8b": llama3_8b,
 }
 
 

@@ -11,8 +11,11 @@ and ``ops.swiglu`` between the two MLP GEMMs.  The head is the token embedding (
 
 Labels are NOT shifted here (the GPT-2 convention): ``labels[b, s]`` is the token at ``s + 1``.
 
-Head dimension 64 takes the native kernels; any other even head dimension runs through the references of
-``ops.rope_qkv`` and ``ops.attention``.
+Head dimension 64 takes the native kernels everywhere.  Head dimension 128 (``llama2_7b``, ``llama3_8b``,
+Mistral-7B's shape) takes them for the per-token decode step -- ``ops.attention_decode_gqa`` and the cache fill
+``ops.kv_cache_fill_gqa`` -- so a ``decode_step`` and the captured step of ``generate(use_graph=True)`` hold no
+reference-path attention; its training forward, its prefill (``ops.rope_qkv``'s reference plus SDPA) and
+``extend`` keep the references.  Any other even head dimension runs through the references throughout.
 
 Generation (``generate``, GPT-2's contract): ``prefill`` runs the causal forward once over the right-padded
 prompts, copies every layer's rotated keys and its values into a ``LlamaKVCache`` -- ``[L, 2, B, Hkv, C, D]``:
@@ -468,7 +471,8 @@ def _make(**kw) -> LlamaForCausalLM:
 
 
 def llama_tiny(**kw) -> LlamaForCausalLM:
-    """2 layers, hidden 128, 2 heads over 1 KV head (head dim 64), vocabulary 1000: the code path at test size."""
+    """2 layers, hidden 128, 2 heads over 1 KV head (head dim 64), vocabulary 1000: the code path at test size.
+    ``llama_tiny(hidden_size=256)`` is the same at head dim 128."""
     d = dict(hidden_size=128, num_hidden_layers=2, num_attention_heads=2, num_key_value_heads=1,
              intermediate_size=352, vocab_size=1000, max_position_embeddings=256)
     d.update(kw)
@@ -489,6 +493,25 @@ def smollm_360m(**kw) -> LlamaForCausalLM:
 def smollm_1p7b(**kw) -> LlamaForCausalLM:
     d = dict(hidden_size=2048, num_hidden_layers=24, num_attention_heads=32, num_key_value_heads=32,
              intermediate_size=8192)
+    d.update(kw)
+    return _make(**d)
+
+
+def llama2_7b(**kw) -> LlamaForCausalLM:
+    """Llama-2-7B's shape: 32 / 32 heads of dim 128, untied head.  (Tests and benchmarks cut
+    ``num_hidden_layers`` down.)"""
+    d = dict(hidden_size=4096, num_hidden_layers=32, num_attention_heads=32, num_key_value_heads=32,
+             intermediate_size=11008, vocab_size=32000, max_position_embeddings=4096, rope_theta=1e4,
+             tie_word_embeddings=False)
+    d.update(kw)
+    return _make(**d)
+
+
+def llama3_8b(**kw) -> LlamaForCausalLM:
+    """Llama-3-8B's shape: 32 query heads over 8 KV heads of dim 128, untied head."""
+    d = dict(hidden_size=4096, num_hidden_layers=32, num_attention_heads=32, num_key_value_heads=8,
+             intermediate_size=14336, vocab_size=128256, max_position_embeddings=8192, rope_theta=5e5,
+             tie_word_embeddings=False)
     d.update(kw)
     return _make(**d)
 

@@ -2,6 +2,11 @@
 (csrc/kernels/attn_extend.hip) -- and the cache fill after a prefill; for GPT-2's packed projection and, with a
 rotary ``table``, for the Llama family's grouped-query cache of rotated keys.
 
+Head dimension 64 throughout, except the rotary decode and its cache fill, which also have head-dim-128
+instances (csrc/kernels/attn_decode_d128.hip: Llama-2-7B, Llama-3-8B, Mistral-7B).  ``attention_decode_gqa`` and
+``kv_cache_fill_gqa`` read D from the cache; everything else here is D = 64 only -- no D = 128 extend, no
+D = 128 instance of GPT-2's non-rotary decode (no GPT-2 has that head size), no other head dimensions.
+
 No autograd: generation runs under ``torch.no_grad()``.  ``lens`` and ``new_lens`` stay on the device; the launch
 grids follow from the shapes and from ``max_len`` (the host's bound on ``lens``) alone, so no call synchronises.
 """
@@ -31,9 +36,14 @@ _lib.register({
     "ddl_attn_extend_gqa_supported": [I, I],
     "ddl_attn_extend_gqa_tile": [I, I, I],
     "ddl_attn_extend_gqa": [P, P, P, P, P, P, P, I, I, I, I, I, I, L, CF, P],
+    "ddl_attn_decode_gqa_supported_hd": [I, I, I],
+    "ddl_attn_decode_gqa_ws_hd": [I, I, I, I, I],
+    "ddl_attn_decode_gqa_d128": [P, P, P, P, P, P, P, I, I, I, I, I, L, CF, P],
+    "ddl_kv_cache_fill_gqa_d128": [P, P, P, I, I, I, I, I, P],
 })
 
 _SCALE = 1.0 / math.sqrt(64)
+DECODE_HEAD_DIMS = (64, 128)        # of attention_decode_gqa and kv_cache_fill_gqa
 
 
 def plan(B: int, H: int, max_len: int):
@@ -42,17 +52,33 @@ def plan(B: int, H: int, max_len: int):
 
 
 def plan_gqa(B: int, Hkv: int, max_len: int):
-    """(nsplit, chunk) of ``attention_decode_gqa``."""
+    """(nsplit, chunk) of ``attention_decode_gqa``, at either head dimension: the plan follows from B, Hkv and
+    ``max_len`` alone (a chunk is a multiple of 32 positions: of the 32 key groups of a D = 64 workgroup and of
+    the 16 of a D = 128 one)."""
     return (_lib.fn("ddl_attn_decode_gqa_nsplit")(B, Hkv, max_len),
             _lib.fn("ddl_attn_decode_gqa_chunk")(B, Hkv, max_len))
 
 
-def supported(num_heads: int, num_kv_heads: int) -> bool:
+def supported(num_heads: int, num_kv_heads: int, head_dim: int = 64) -> bool:
     """The rotary kernels have an instance for this group size (G in 1, 2, 3, 4, 8).  Decode and extend are built
-    for the same set and ``ops.attention`` routes a model's cache through both, so one answer serves both: a group
-    size either kernel lacks takes the reference for the whole cache, never for one of the two paths alone."""
-    return bool(_lib.fn("ddl_attn_decode_gqa_supported")(num_heads, num_kv_heads)
+    for the same set and ``ops.attention`` routes a model's cache through both, so at head dim 64 one answer serves
+    both: a group size either kernel lacks takes the reference for the whole cache, never for one of the two paths
+    alone.  At ``head_dim=128`` only decode (and the fill) exist, so the answer for both paths is False: ask
+    ``supported_decode``."""
+    return bool(head_dim == 64 and _lib.fn("ddl_attn_decode_gqa_supported")(num_heads, num_kv_heads)
                 and _lib.fn("ddl_attn_extend_gqa_supported")(num_heads, num_kv_heads))
+
+
+def supported_decode(num_heads: int, num_kv_heads: int, head_dim: int = 64) -> bool:
+    """What ``attention_decode_gqa`` takes natively.  Head dim 64: ``supported``'s answer (decode never goes
+    native without extend).  Head dim 128: the decode kernel's own -- there the cache is appended to by the native
+    decode and by the REFERENCE extend, which is sound: both append keys rotated in fp32 and rounded once to bf16
+    and bit-copied values, and both read the same ``[B, Hkv, C, D]`` layout of rotated keys, so either continues
+    a cache the other wrote.  The kernel may contract ``a c - b s`` into an FMA where torch rounds the two
+    products, so an appended key element can differ by one bf16 ulp between the two paths."""
+    if head_dim == 64:
+        return supported(num_heads, num_kv_heads)
+    return bool(_lib.fn("ddl_attn_decode_gqa_supported_hd")(num_heads, num_kv_heads, head_dim))
 
 
 def tile(T: int, num_heads: int, num_kv_heads: int) -> int:
@@ -60,13 +86,15 @@ def tile(T: int, num_heads: int, num_kv_heads: int) -> int:
     return _lib.fn("ddl_attn_extend_gqa_tile")(T, num_heads, num_kv_heads)
 
 
-def _check_cache(cache_k, cache_v, B, heads, name="H"):
+def _check_cache(cache_k, cache_v, B, heads, name="H", dims=(64,)):
+    """-> the head dimension, one of ``dims``."""
     if cache_k.shape != cache_v.shape or cache_k.dim() != 4 or cache_k.shape[0] != B or cache_k.shape[1] != heads \
-            or cache_k.shape[3] != 64:
-        raise ValueError(f"cache must be [B={B}, {name}={heads}, C, 64] for keys and values, got "
-                         f"{tuple(cache_k.shape)} / {tuple(cache_v.shape)}")
+            or cache_k.shape[3] not in dims:
+        raise ValueError(f"cache must be [B={B}, {name}={heads}, C, {' or '.join(map(str, dims))}] for keys and "
+                         f"values, got {tuple(cache_k.shape)} / {tuple(cache_v.shape)}")
     if not (cache_k.is_contiguous() and cache_v.is_contiguous()):
         raise ValueError("cache tensors must be contiguous")
+    return cache_k.shape[3]
 
 
 def _workspace(ws_fn: str, dev, *args):
@@ -91,14 +119,17 @@ def attention_decode(qkv_new, cache_k, cache_v, lens, num_heads, max_len):
 
 def attention_decode_gqa(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len):
     B, H, Hkv = qkv_new.shape[0], num_heads, num_kv_heads
-    _check_cache(cache_k, cache_v, B, Hkv, "Hkv")
+    D = _check_cache(cache_k, cache_v, B, Hkv, "Hkv", DECODE_HEAD_DIMS)
+    if qkv_new.shape[1] != (H + 2 * Hkv) * D or table.shape[1] != D:
+        raise ValueError(f"qkv_new must be [B, (H + 2 Hkv) {D}] and table [n_positions, {D}], got "
+                         f"{tuple(qkv_new.shape)} / {tuple(table.shape)}")
     _check_lens(B, lens)
     qkv_new, table = qkv_new.contiguous(), table.contiguous()
-    out = torch.empty(B, H * 64, dtype=qkv_new.dtype, device=qkv_new.device)
-    ws = _workspace("ddl_attn_decode_gqa_ws", qkv_new.device, B, H, Hkv, max_len)
-    _lib.call("ddl_attn_decode_gqa", qkv_new.data_ptr(), table.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(),
-              lens.data_ptr(), out.data_ptr(), _lib.p(ws), B, H, Hkv, cache_k.shape[2], max_len, table.shape[0],
-              _SCALE)
+    out = torch.empty(B, H * D, dtype=qkv_new.dtype, device=qkv_new.device)
+    ws = _workspace("ddl_attn_decode_gqa_ws_hd", qkv_new.device, B, H, Hkv, max_len, D)
+    _lib.call("ddl_attn_decode_gqa" if D == 64 else "ddl_attn_decode_gqa_d128", qkv_new.data_ptr(), table.data_ptr(),
+              cache_k.data_ptr(), cache_v.data_ptr(), lens.data_ptr(), out.data_ptr(), _lib.p(ws), B, H, Hkv,
+              cache_k.shape[2], max_len, table.shape[0], 1.0 / math.sqrt(D))
     return out
 
 
@@ -135,7 +166,9 @@ def kv_cache_fill(qkv, cache_k, cache_v, num_heads):
 
 def kv_cache_fill_gqa(packed, cache_k, cache_v, num_heads, num_kv_heads):
     B, S, _ = packed.shape
-    _check_cache(cache_k, cache_v, B, num_kv_heads, "Hkv")
+    D = _check_cache(cache_k, cache_v, B, num_kv_heads, "Hkv", DECODE_HEAD_DIMS)
+    if packed.shape[2] != 3 * num_heads * D:
+        raise ValueError(f"packed must be rope_qkv's [B, S, 3 H {D}], got {tuple(packed.shape)}")
     packed = packed.contiguous()
-    _lib.call("ddl_kv_cache_fill_gqa", packed.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(), B, S, num_heads,
+    _lib.call("ddl_kv_cache_fill_gqa" if D == 64 else "ddl_kv_cache_fill_gqa_d128", packed.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(), B, S, num_heads,
               num_kv_heads, cache_k.shape[2])
