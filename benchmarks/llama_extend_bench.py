@@ -18,6 +18,15 @@ best of ``--reps`` runs after one warm-up run of each arm, the arms alternating 
         the n + T expanded key rows in place (it neither rotates, gathers nor appends).
 (c) ``prefill(chunk=128)`` against the whole ``prefill`` at S = 1024, B = 16: time and
     ``torch.cuda.max_memory_allocated`` above what was allocated before the call, on one preallocated cache.
+
+``--head-dim 128`` runs the head-dimension-128 study instead (csrc/kernels/attn_extend_d128.hip):
+(d) ``ops.attention_extend_gqa`` at D = 128 for (H, Hkv) in {(32, 8), (32, 32)}, B in {1, 16}, T in {16, 64, 128,
+    512} over n in {896, 8191} cached keys, timed as in (b) against ``ops.attention_extend_gqa_reference`` on the
+    same tensors (what every D = 128 extend ran before) and the masked SDPA of (b).  Each line carries the bytes
+    the kernel must read (n cached K and V rows of Hkv heads, the chunk, its table rows) and the MFMA FLOPs,
+    both from the shapes; ``floor_bound`` marks a call time within 1.5x of the ~20 us enqueue floor, which bounds
+    the kernel from above and does not measure it.
+(e) (a) for ``llama3_8b(num_hidden_layers=4)``.
 """
 import argparse
 import json
@@ -62,17 +71,17 @@ def _alternate(arms, reps):
     return {name: min(v) for name, v in times.items()}, times
 
 
-def _model(dev):
+def _model(dev, name="smollm_135m", **kw):
     import torch
     from databricks_distributed_deep_learning_amd import models
     from databricks_distributed_deep_learning_amd.models import cast_params
     torch.manual_seed(0)
-    model = models.smollm_135m().to(dev).eval()
+    model = getattr(models, name)(**kw).to(dev).eval()
     cast_params(model, torch.bfloat16)
     return model
 
 
-def bench_ttft(model, dev, reps):
+def bench_ttft(model, dev, reps, name="smollm_135m"):
     import torch
     from databricks_distributed_deep_learning_amd.models import LlamaKVCache
     P, T = 896, 64
@@ -97,7 +106,7 @@ def bench_ttft(model, dev, reps):
 
         best, times = _alternate([("reuse", reuse), ("full", full)], reps)
         agree = (out["reuse"].argmax(-1) == out["full"].argmax(-1)).float().mean().item()
-        print(json.dumps({"ttft": "smollm_135m", "B": B, "prefix": P, "new": T,
+        print(json.dumps({"ttft": name, "B": B, "prefix": P, "new": T,
                           "reuse_ms": round(best["reuse"] * 1e3, 3), "full_prefill_ms": round(best["full"] * 1e3, 3),
                           "speedup": round(best["full"] / best["reuse"], 2),
                           "reuse_faster": bool(best["reuse"] < best["full"]), "argmax_agreement": round(agree, 4),
@@ -157,6 +166,65 @@ def bench_kernel(dev, reps):
             del data, wide
 
 
+ENQUEUE_FLOOR_US = 20.0
+
+
+def bench_kernel_d128(dev, reps):
+    import torch
+    import torch.nn.functional as F
+    from databricks_distributed_deep_learning_amd import ops
+    from databricks_distributed_deep_learning_amd.ops.attention import attention_extend_gqa_reference as ref_fn
+    D, TS = 128, (16, 64, 128, 512)
+    table = ops.rope_table(8192 + 512, 500000.0, D, dev)
+    for H, Hkv in ((32, 8), (32, 32)):
+        G = H // Hkv
+        for B in (1, 16):
+            for n in (896, 8191):
+                C = n + max(TS)
+                per_layer = 2 * B * Hkv * C * D * 2
+                L = min(64, -(-ROTATE_BYTES // per_layer))
+                data = torch.randn(L, 2, B, Hkv, C, D, device=dev).bfloat16()
+                wide = data.repeat_interleave(G, 3) if G > 1 else data      # the cache expanded to H heads
+                lens = torch.full((B,), n, dtype=torch.int32, device=dev)
+                for T in TS:
+                    qkv = torch.randn(B, T, (H + 2 * Hkv) * D, device=dev).bfloat16()
+                    q = ops.rope_qkv(qkv, table[n:n + T].contiguous(), H, Hkv).view(B, T, 3, H, D)[:, :, 0].transpose(1, 2)
+                    j, i = torch.arange(n + T, device=dev), torch.arange(T, device=dev)
+                    mask = j[None, :] <= n + i[:, None]
+
+                    def ours(k):
+                        ops.attention_extend_gqa(qkv, table, data[k % L, 0], data[k % L, 1], lens, H, Hkv, n)
+
+                    def reference(k):
+                        ref_fn(qkv, table, data[k % L, 0], data[k % L, 1], lens, H, Hkv, n)
+
+                    def sdpa(k):
+                        F.scaled_dot_product_attention(q, wide[k % L, 0, :, :, :n + T], wide[k % L, 1, :, :, :n + T],
+                                                       attn_mask=mask)
+
+                    arms = (("ours", ours), ("reference", reference), ("sdpa", sdpa))
+                    iters = {}
+                    for name, fn in arms:       # warm-up; then as many calls as fit ~50 ms, 3 .. 200
+                        fn(0)
+                        iters[name] = int(min(200, max(3, 5e4 / _events(fn, 3))))
+                    t = {name: [] for name, _ in arms}
+                    for _ in range(reps):
+                        for name, fn in arms:
+                            t[name].append(_events(fn, iters[name]))
+                    t = {name: min(v) for name, v in t.items()}
+                    flops = 4.0 * B * H * D * T * (n + (T + 1) / 2)
+                    read = 2 * B * Hkv * n * D * 2 + B * T * (H + 2 * Hkv) * D * 2 + T * D * 4
+                    print(json.dumps({"kernel": "attention_extend_gqa_d128", "B": B, "H": H, "Hkv": Hkv, "n": n, "T": T,
+                                      "copies": L, "us": round(t["ours"], 2), "reference_us": round(t["reference"], 2),
+                                      "sdpa_masked_us": round(t["sdpa"], 2), "min_read_MB": round(read / 1e6, 2),
+                                      "mfma_GFLOP": round(flops / 1e9, 3), "TFLOPs": round(flops / t["ours"] / 1e6, 2),
+                                      "GBps": round(read / t["ours"] / 1e3, 1),
+                                      "floor_bound": bool(t["ours"] < 1.5 * ENQUEUE_FLOOR_US),
+                                      "faster_than_reference": bool(t["ours"] < t["reference"]),
+                                      "faster_than_sdpa": bool(t["ours"] < t["sdpa"])}), flush=True)
+                del data, wide
+
+
 def bench_chunked(model, dev, reps):
     import torch
     from databricks_distributed_deep_learning_amd.models import LlamaKVCache
@@ -194,11 +262,19 @@ def main() -> int:
     ap.add_argument("--skip-ttft", action="store_true")
     ap.add_argument("--skip-kernel", action="store_true")
     ap.add_argument("--skip-chunked", action="store_true")
+    ap.add_argument("--head-dim", type=int, default=64, choices=(64, 128))
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("llama_extend_bench needs a GPU: times are not measured without one")
     dev = torch.device("cuda", 0)
+    if args.head_dim == 128:
+        with torch.no_grad():
+            if not args.skip_kernel:
+                bench_kernel_d128(dev, args.reps)
+            if not args.skip_ttft:
+                bench_ttft(_model(dev, "llama3_8b", num_hidden_layers=4), dev, args.reps, "llama3_8b(num_hidden_layers=4)")
+        return 0
     model = None if args.skip_ttft and args.skip_chunked else _model(dev)
     with torch.no_grad():
         if not args.skip_ttft:

@@ -12,10 +12,11 @@ and ``ops.swiglu`` between the two MLP GEMMs.  The head is the token embedding (
 Labels are NOT shifted here (the GPT-2 convention): ``labels[b, s]`` is the token at ``s + 1``.
 
 Head dimension 64 takes the native kernels everywhere.  Head dimension 128 (``llama2_7b``, ``llama3_8b``,
-Mistral-7B's shape) takes them for the per-token decode step -- ``ops.attention_decode_gqa`` and the cache fill
-``ops.kv_cache_fill_gqa`` -- so a ``decode_step`` and the captured step of ``generate(use_graph=True)`` hold no
-reference-path attention; its training forward, its prefill (``ops.rope_qkv``'s reference plus SDPA) and
-``extend`` keep the references.  Any other even head dimension runs through the references throughout.
+Mistral-7B's shape) takes them for every attention call on a cache -- ``ops.attention_decode_gqa``,
+``ops.attention_extend_gqa`` and the cache fill ``ops.kv_cache_fill_gqa`` -- so a ``decode_step``, the captured
+step of ``generate(use_graph=True)``, ``extend``, ``prefill(chunk=)`` and ``generate(prefix=)`` hold no
+reference-path attention; its training forward and its whole-prompt prefill (``ops.rope_qkv``'s reference plus
+SDPA) keep the references.  Any other even head dimension runs through the references throughout.
 
 Generation (``generate``, GPT-2's contract): ``prefill`` runs the causal forward once over the right-padded
 prompts, copies every layer's rotated keys and its values into a ``LlamaKVCache`` -- ``[L, 2, B, Hkv, C, D]``:

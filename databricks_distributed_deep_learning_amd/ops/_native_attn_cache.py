@@ -2,10 +2,11 @@
 (csrc/kernels/attn_extend.hip) -- and the cache fill after a prefill; for GPT-2's packed projection and, with a
 rotary ``table``, for the Llama family's grouped-query cache of rotated keys.
 
-Head dimension 64 throughout, except the rotary decode and its cache fill, which also have head-dim-128
-instances (csrc/kernels/attn_decode_d128.hip: Llama-2-7B, Llama-3-8B, Mistral-7B).  ``attention_decode_gqa`` and
-``kv_cache_fill_gqa`` read D from the cache; everything else here is D = 64 only -- no D = 128 extend, no
-D = 128 instance of GPT-2's non-rotary decode (no GPT-2 has that head size), no other head dimensions.
+Head dimension 64 throughout, except the rotary kernels, which also have head-dim-128 instances (Llama-2-7B,
+Llama-3-8B, Mistral-7B): decode and the cache fill in csrc/kernels/attn_decode_d128.hip, extend in
+csrc/kernels/attn_extend_d128.hip.  ``attention_decode_gqa``, ``attention_extend_gqa`` and ``kv_cache_fill_gqa``
+read D from the cache; GPT-2's non-rotary ops are D = 64 only (no GPT-2 has another head size), and there are
+no other head dimensions.
 
 No autograd: generation runs under ``torch.no_grad()``.  ``lens`` and ``new_lens`` stay on the device; the launch
 grids follow from the shapes and from ``max_len`` (the host's bound on ``lens``) alone, so no call synchronises.
@@ -40,10 +41,13 @@ _lib.register({
     "ddl_attn_decode_gqa_ws_hd": [I, I, I, I, I],
     "ddl_attn_decode_gqa_d128": [P, P, P, P, P, P, P, I, I, I, I, I, L, CF, P],
     "ddl_kv_cache_fill_gqa_d128": [P, P, P, I, I, I, I, I, P],
+    "ddl_attn_extend_gqa_d128_supported": [I, I],
+    "ddl_attn_extend_gqa_d128_tile": [I, I, I],
+    "ddl_attn_extend_gqa_d128": [P, P, P, P, P, P, P, I, I, I, I, I, I, L, CF, P],
 })
 
 _SCALE = 1.0 / math.sqrt(64)
-DECODE_HEAD_DIMS = (64, 128)        # of attention_decode_gqa and kv_cache_fill_gqa
+DECODE_HEAD_DIMS = (64, 128)        # of attention_decode_gqa, attention_extend_gqa and kv_cache_fill_gqa
 
 
 def plan(B: int, H: int, max_len: int):
@@ -60,30 +64,42 @@ def plan_gqa(B: int, Hkv: int, max_len: int):
 
 
 def supported(num_heads: int, num_kv_heads: int, head_dim: int = 64) -> bool:
-    """The rotary kernels have an instance for this group size (G in 1, 2, 3, 4, 8).  Decode and extend are built
-    for the same set and ``ops.attention`` routes a model's cache through both, so at head dim 64 one answer serves
-    both: a group size either kernel lacks takes the reference for the whole cache, never for one of the two paths
-    alone.  At ``head_dim=128`` only decode (and the fill) exist, so the answer for both paths is False: ask
-    ``supported_decode``."""
+    """The D = 64 pair of rotary kernels has an instance for this group size (G in 1, 2, 3, 4, 8).  Decode and
+    extend are built for the same set and ``ops.attention`` routes a model's cache through both, so at head dim 64
+    one answer serves both: a group size either kernel lacks takes the reference for the whole cache, never for
+    one of the two paths alone.  This is about that pair only: at any other ``head_dim`` the answer is False.  The
+    head-dim-128 kernels are separate files and answer for themselves: ask ``supported_decode`` and
+    ``supported_extend``."""
     return bool(head_dim == 64 and _lib.fn("ddl_attn_decode_gqa_supported")(num_heads, num_kv_heads)
                 and _lib.fn("ddl_attn_extend_gqa_supported")(num_heads, num_kv_heads))
 
 
 def supported_decode(num_heads: int, num_kv_heads: int, head_dim: int = 64) -> bool:
     """What ``attention_decode_gqa`` takes natively.  Head dim 64: ``supported``'s answer (decode never goes
-    native without extend).  Head dim 128: the decode kernel's own -- there the cache is appended to by the native
-    decode and by the REFERENCE extend, which is sound: both append keys rotated in fp32 and rounded once to bf16
-    and bit-copied values, and both read the same ``[B, Hkv, C, D]`` layout of rotated keys, so either continues
-    a cache the other wrote.  The kernel may contract ``a c - b s`` into an FMA where torch rounds the two
-    products, so an appended key element can differ by one bf16 ulp between the two paths."""
+    native without extend).  Head dim 128: the decode kernel's own.  A cache may be appended to by a native kernel
+    and by a reference (another dtype, a prefill), which is sound: all append keys rotated in fp32 and rounded
+    once to bf16 and bit-copied values, and all read the same ``[B, Hkv, C, D]`` layout of rotated keys, so any
+    continues a cache another wrote.  A kernel may contract ``a c - b s`` into an FMA where torch rounds the two
+    products, so an appended key element can differ by one bf16 ulp between a kernel and a reference."""
     if head_dim == 64:
         return supported(num_heads, num_kv_heads)
     return bool(_lib.fn("ddl_attn_decode_gqa_supported_hd")(num_heads, num_kv_heads, head_dim))
 
 
-def tile(T: int, num_heads: int, num_kv_heads: int) -> int:
+def supported_extend(num_heads: int, num_kv_heads: int, head_dim: int = 64) -> bool:
+    """What ``attention_extend_gqa`` takes natively.  Head dim 64: ``supported``'s answer.  Head dim 128: the
+    head-dim-128 extend kernel's own."""
+    if head_dim == 64:
+        return supported(num_heads, num_kv_heads)
+    return bool(head_dim == 128 and _lib.fn("ddl_attn_extend_gqa_d128_supported")(num_heads, num_kv_heads))
+
+
+def tile(T: int, num_heads: int, num_kv_heads: int, head_dim: int = 64) -> int:
     """Queries per workgroup ``attention_extend_gqa`` uses for a chunk of ``T`` tokens (0 without an instance)."""
-    return _lib.fn("ddl_attn_extend_gqa_tile")(T, num_heads, num_kv_heads)
+    if head_dim not in DECODE_HEAD_DIMS:
+        return 0
+    return _lib.fn("ddl_attn_extend_gqa_tile" if head_dim == 64 else "ddl_attn_extend_gqa_d128_tile")(
+        T, num_heads, num_kv_heads)
 
 
 def _check_cache(cache_k, cache_v, B, heads, name="H", dims=(64,)):
@@ -146,13 +162,16 @@ def attention_extend(qkv_new, cache_k, cache_v, lens, num_heads, max_len, new_le
 
 def attention_extend_gqa(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len, new_lens=None):
     B, T, H, Hkv = qkv_new.shape[0], qkv_new.shape[1], num_heads, num_kv_heads
-    _check_cache(cache_k, cache_v, B, Hkv, "Hkv")
+    D = _check_cache(cache_k, cache_v, B, Hkv, "Hkv", DECODE_HEAD_DIMS)
+    if qkv_new.shape[2] != (H + 2 * Hkv) * D or table.shape[1] != D:
+        raise ValueError(f"qkv_new must be [B, T, (H + 2 Hkv) {D}] and table [n_positions, {D}], got "
+                         f"{tuple(qkv_new.shape)} / {tuple(table.shape)}")
     _check_lens(B, lens, new_lens)
     qkv_new, table = qkv_new.contiguous(), table.contiguous()
-    out = torch.empty(B, T, H * 64, dtype=qkv_new.dtype, device=qkv_new.device)
-    _lib.call("ddl_attn_extend_gqa", qkv_new.data_ptr(), table.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(),
-              lens.data_ptr(), _lib.p(new_lens), out.data_ptr(), B, T, H, Hkv, cache_k.shape[2], max_len,
-              table.shape[0], _SCALE)
+    out = torch.empty(B, T, H * D, dtype=qkv_new.dtype, device=qkv_new.device)
+    _lib.call("ddl_attn_extend_gqa" if D == 64 else "ddl_attn_extend_gqa_d128", qkv_new.data_ptr(), table.data_ptr(),
+              cache_k.data_ptr(), cache_v.data_ptr(), lens.data_ptr(), _lib.p(new_lens), out.data_ptr(), B, T, H, Hkv,
+              cache_k.shape[2], max_len, table.shape[0], 1.0 / math.sqrt(D))
     return out
 
 

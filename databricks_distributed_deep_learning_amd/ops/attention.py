@@ -361,9 +361,9 @@ def attention_decode_gqa_reference(qkv_new: torch.Tensor, table: torch.Tensor, c
 def attention_decode_gqa(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
                          lens: torch.Tensor, num_heads: int, num_kv_heads: int, max_len: int) -> torch.Tensor:
     """Grouped-query single-query attention over the rotated cache, with the new token's rotation and the
-    append; returns ``[B, H·D]``.  Native at head dimension 64 and 128 (bf16, G in 1, 2, 3, 4, 8); at 128 only
-    this op and ``kv_cache_fill_gqa`` are: ``attention_extend_gqa``, ``rope_qkv`` and ``attention`` keep their
-    references there, and every other head dimension takes the reference here too."""
+    append; returns ``[B, H·D]``.  Native at head dimension 64 and 128 (bf16, G in 1, 2, 3, 4, 8); at 128 this op,
+    ``attention_extend_gqa`` and ``kv_cache_fill_gqa`` are: ``rope_qkv`` and ``attention`` (a whole-prompt prefill,
+    training) keep their references there, and every other head dimension takes the reference here too."""
     D = _decode_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len)
     if (_lib.use_native(qkv_new, table, cache_k, cache_v, lens) and qkv_new.dtype == torch.bfloat16
             and cache_k.dtype == torch.bfloat16 and cache_v.dtype == torch.bfloat16
@@ -488,15 +488,15 @@ def attention_extend_gqa(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: to
                          lens: torch.Tensor, num_heads: int, num_kv_heads: int, max_len: int,
                          new_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Grouped-query causal attention of a chunk of new tokens over the rotated cache plus the chunk, with the
-    chunk's rotation and the append; returns ``[B, T, H·D]``.  Native at head dimension 64 only: at 128 this is the
-    reference, on a cache the native decode also appends to (``_native_attn_cache.supported_decode`` says why
-    that is sound)."""
+    chunk's rotation and the append; returns ``[B, T, H·D]``.  Native at head dimension 64 and 128 (bf16, G in 1, 2,
+    3, 4, 8; csrc/kernels/attn_extend.hip and attn_extend_d128.hip); every other case is the reference, which may
+    share a cache with the kernels (``_native_attn_cache.supported_decode`` says why that is sound)."""
     D = _extend_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len, new_lens)
     if (_lib.use_native(qkv_new, table, cache_k, cache_v, lens, new_lens) and qkv_new.dtype == torch.bfloat16
             and cache_k.dtype == torch.bfloat16 and cache_v.dtype == torch.bfloat16
-            and table.dtype == torch.float32 and D == 64):
+            and table.dtype == torch.float32 and D in (64, 128)):
         from . import _native_attn_cache as N
-        if N.supported(num_heads, num_kv_heads):
+        if N.supported_extend(num_heads, num_kv_heads, D):
             return N.attention_extend_gqa(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len,
                                           new_lens)
     return attention_extend_gqa_reference(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len,
