@@ -30,12 +30,16 @@ def round_capacity(need: int, n_positions: int) -> int:
 
 def _key(model, batch: int, capacity: int, graph: bool, ext: bool = False):
     w = model._session_weight()
-    return (batch, capacity, w.device, w.dtype, graph, ext, tuple(p.data_ptr() for p in model.parameters()))
+    # (a model may name further tensors its step reads, such as quantised decode weights, in _session_tensors)
+    more = getattr(model, "_session_tensors", lambda: ())()
+    return (batch, capacity, w.device, w.dtype, graph, ext, tuple(p.data_ptr() for p in model.parameters()),
+            tuple(t.data_ptr() for t in more))
 
 
 def session_for(model, batch: int, capacity: int, graph: bool, ext: bool = False) -> "DecodeSession":
     """The model's session for this shape: rebuilt when the batch, the capacity, the device, the dtype or
-    the address of any parameter baked into the captured step has changed.  ``ext``: a session whose step
+    the address of any parameter (or of any tensor of the model's ``_session_tensors()``) baked into the captured
+    step has changed.  ``ext``: a session whose step
     also serves top-p, min-p and a repetition penalty (another launch in the captured step, so part of the
     key); without it the step is the one it always was."""
     key = _key(model, batch, capacity, graph, ext)

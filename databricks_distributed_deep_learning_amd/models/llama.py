@@ -142,6 +142,22 @@ class LlamaBlock(nn.Module):
         self.post_attention_layernorm = RMSNorm(E, c.rms_norm_eps)
         self.gate_up = Linear(E, 2 * c.intermediate_size, bias=False, init_std=std)
         self.down_proj = Linear(c.intermediate_size, E, bias=False, init_std=std)
+        # {name: (wq, scale)} of the four linears once ``quantize_decode_weights`` has run.  A plain attribute,
+        # not buffers: a dtype cast would turn e4m3 bytes and fp32 scales into bf16, and ``state_dict()`` stays
+        # what it was.
+        self._fp8 = None
+
+    def _apply(self, fn, recurse=True):
+        # a cast or a move leaves the quantised snapshot behind: drop it (the caller quantises again)
+        self._fp8 = None
+        return super()._apply(fn, recurse)
+
+    def _lin(self, name, x, residual=None):
+        """The M <= 16 linear ``name`` of a decode step: from the FP8 pair when there is one."""
+        if self._fp8 is not None:
+            wq, scale = self._fp8[name]
+            return ops.linear_small_m_fp8(x, wq, scale, None, residual=residual)
+        return ops.linear_small_m(x, getattr(self, name).weight, None, residual=residual)
 
     def forward(self, h, table, mask=None, positions=None, doc=None):
         """``positions`` / ``doc`` (packed rows): the int32 rotary positions and ``ops.doc_bounds``' pair."""
@@ -170,18 +186,17 @@ class LlamaBlock(nn.Module):
         """One new token per sequence, ``h_new [B, E]``, against the cache (which gains its rotated key and
         its value).  ``len_bound``: the bound on ``lens + 1`` that sizes the attention launch (default
         ``max_len + 1``)."""
-        lin = ops.linear_small_m
-        qkv = lin(self.input_layernorm(h_new), self.qkv.weight, None)
+        qkv = self._lin("qkv", self.input_layernorm(h_new))
         ctx = ops.attention_decode_gqa(qkv, table, cache.k(layer), cache.v(layer), cache.lens, self.num_heads,
                                        self.num_kv_heads, cache.max_len + 1 if len_bound is None else len_bound)
         return self._small_m_tail(ctx, h_new)
 
     def _small_m_tail(self, ctx, h):
-        """Output projection and MLP of a block on M <= 16 rows (``ops.linear_small_m``)."""
-        lin = ops.linear_small_m
-        h = lin(ctx, self.o_proj.weight, None, residual=h)
-        z = ops.swiglu(lin(self.post_attention_layernorm(h), self.gate_up.weight, None))
-        return lin(z, self.down_proj.weight, None, residual=h)
+        """Output projection and MLP of a block on M <= 16 rows (``ops.linear_small_m``, or
+        ``ops.linear_small_m_fp8`` on quantised decode weights)."""
+        h = self._lin("o_proj", ctx, residual=h)
+        z = ops.swiglu(self._lin("gate_up", self.post_attention_layernorm(h)))
+        return self._lin("down_proj", z, residual=h)
 
     def extend(self, h, table, cache: LlamaKVCache, layer: int, new_lens=None, len_bound=None):
         """A chunk of new tokens per sequence, ``h [B, T, E]``, against the cache, which gains the rotated keys
@@ -190,7 +205,7 @@ class LlamaBlock(nn.Module):
         (default ``max_len``).  With ``B T <= 16`` the linears are the weight-streaming ones of ``decode``."""
         small = h.shape[0] * h.shape[1] <= 16
         y = self.input_layernorm(h)
-        qkv = ops.linear_small_m(y, self.qkv.weight, None) if small else self.qkv(y)
+        qkv = self._lin("qkv", y) if small else self.qkv(y)
         ctx = ops.attention_extend_gqa(qkv, table, cache.k(layer), cache.v(layer), cache.lens, self.num_heads,
                                        self.num_kv_heads, cache.max_len if len_bound is None else len_bound,
                                        new_lens)
@@ -237,6 +252,38 @@ class LlamaForCausalLM(nn.Module):
 
     def head_weight(self) -> torch.Tensor:
         return self.embed_tokens.weight if self.lm_head is None else self.lm_head.weight
+
+    # ------------------------------------------------------------ FP8 decode weights
+    DECODE_LINEARS = ("qkv", "o_proj", "gate_up", "down_proj")
+
+    def quantize_decode_weights(self, fmt: str = "fp8") -> "LlamaForCausalLM":
+        """Quantise every block's ``qkv``, ``o_proj``, ``gate_up`` and ``down_proj`` weight to FP8
+        (``ops.quantize_fp8_rows``: e4m3 with one fp32 scale per output row) and keep the pair next to the bf16
+        weight.  From then on the M <= 16 paths -- ``decode_step``, the captured step of
+        ``generate(use_graph=True)`` and ``extend`` with ``B T <= 16`` -- stream the FP8 bytes through
+        ``ops.linear_small_m_fp8``: half the weight traffic of a step.
+
+        The bf16 parameters stay and nothing else reads the pairs: ``forward``, training, ``prefill``,
+        ``extend`` above 16 rows, ``state_dict()`` and the HF conversion are unchanged, and the embedding and the
+        head stay bf16.  So this buys decode time and costs 0.5x the block weights in extra memory; it is not a
+        memory saving.
+
+        The pairs are a snapshot of the weights at this call: after they change (``load_state_dict``, an
+        optimizer step) call this again.  Any ``.to(...)`` / ``.bfloat16()`` / ``.float()`` of the model or a
+        block drops them (they are never cast or left behind on another device), as ``clear_decode_weights``
+        does; a decode session captured before either is rebuilt."""
+        if fmt != "fp8":
+            raise ValueError(f"fmt must be 'fp8', got {fmt!r}")
+        with torch.no_grad():
+            for blk in self.layers:
+                blk._fp8 = {n: ops.quantize_fp8_rows(getattr(blk, n).weight) for n in self.DECODE_LINEARS}
+        return self
+
+    def clear_decode_weights(self) -> "LlamaForCausalLM":
+        """Drop the pairs of ``quantize_decode_weights``: decode reads the bf16 weights again."""
+        for blk in self.layers:
+            blk._fp8 = None
+        return self
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, position_ids=None):
         """``token_type_ids`` is ignored: it keeps the training loop's ``(input_ids, attention_mask,
@@ -459,6 +506,10 @@ class LlamaForCausalLM(nn.Module):
     # what a decode session (models/_decode_graph.py) asks of its model
     def _session_weight(self):
         return self.embed_tokens.weight
+
+    def _session_tensors(self):
+        """Tensors the captured step reads that are not parameters: the FP8 decode weights."""
+        return [t for blk in self.layers if blk._fp8 is not None for pair in blk._fp8.values() for t in pair]
 
     def _session_cache(self, batch, capacity, device):
         return LlamaKVCache.allocate(self, batch, capacity, device)

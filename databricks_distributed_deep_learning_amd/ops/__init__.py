@@ -13,7 +13,7 @@ from ._lib import available as native_available, set_mode as set_native_mode, mo
 from ._lib import NativeUnavailable  # noqa: F401
 from .conv import conv2d, conv2d_bias_act, patch_embed  # noqa: F401
 from .norm import batch_norm, batch_norm_add_bn, bn_relu_maxpool, layer_norm  # noqa: F401
-from .linear import linear, linear_small_m  # noqa: F401
+from .linear import linear, linear_small_m, linear_small_m_fp8, quantize_fp8_rows  # noqa: F401
 from .activation import gelu, dropout, relu  # noqa: F401
 from .attention import attention, attention_decode, attention_extend, kv_cache_fill  # noqa: F401
 from .attention import doc_bounds  # noqa: F401

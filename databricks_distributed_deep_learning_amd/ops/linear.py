@@ -81,3 +81,62 @@ def linear_small_m(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] =
         y = _native_linear_decode.linear_small_m(x2, w.contiguous(), b, act, r2)
         return y.view(*x.shape[:-1], N)
     return linear(x, w, b, act, residual=residual)
+
+
+E4M3_MAX = 448.0
+
+
+def quantize_fp8_rows(w: torch.Tensor):
+    """``w [N, K]`` (any float dtype) -> ``(wq, scale)``: ``wq [N, K]`` ``torch.float8_e4m3fn`` and ``scale [N]``
+    fp32 with ``w ~ wq * scale[:, None]``: ``scale[n] = amax_k |w[n, k]| / 448`` (1.0 for an all-zero row), so
+    each row fills the format's range.  Plain torch, run once per weight, on any device.  The quotient is
+    clamped to +-448 before the cast: it can exceed 448 by a rounding, and the cast gives NaN above the
+    format's range."""
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=1)
+    scale = torch.where(amax > 0, amax / E4M3_MAX, torch.ones_like(amax))
+    wq = (wf / scale[:, None]).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+    return wq.contiguous(), scale.contiguous()
+
+
+def _aligned16(*tensors) -> bool:
+    return all(t is None or t.data_ptr() % 16 == 0 for t in tensors)
+
+
+def linear_small_m_fp8(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor, b: Optional[torch.Tensor] = None,
+                       act: Optional[str] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``act((x Wq^T) * scale + b) + residual`` for a decode step's few rows with an FP8 weight
+    (``quantize_fp8_rows``' pair; no autograd): ``wq [N, K]`` is ``torch.float8_e4m3fn`` (or uint8 holding
+    those bits), ``scale [N]`` fp32.  The weight-streaming kernel for M <= 16 rows, bf16 ``x`` / ``b`` /
+    ``residual``, K % 16 == 0 (any N), contiguous ``wq`` and ``scale`` and 16-byte-aligned pointers: it
+    accumulates ``x[m, k] * value(wq[n, k])`` in fp32 with the e4m3 values exact, multiplies the sum by
+    ``scale[n]`` once, then bias, act, residual and one rounding to bf16.
+
+    Everything else runs ``ops.linear(x, (wq.float() * scale[:, None]).to(x.dtype), b, act,
+    residual=residual)``.  That fallback rounds the dequantised weight to ``x``'s dtype: a different,
+    slightly coarser number than the kernel's."""
+    if any(t is not None and t.requires_grad for t in (x, scale, b, residual)) and torch.is_grad_enabled():
+        raise RuntimeError("linear_small_m_fp8 has no autograd: call it under torch.no_grad()")
+    if act not in ACTS:
+        raise ValueError(f"act must be one of {ACTS}")
+    if wq.dtype == torch.uint8:
+        wq = wq.view(torch.float8_e4m3fn)
+    if wq.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"wq must be torch.float8_e4m3fn (or uint8 holding its bits), got {wq.dtype}")
+    K, N = x.shape[-1], wq.shape[0]
+    if wq.dim() != 2 or wq.shape[1] != K or scale.shape != (N,) or (b is not None and b.shape != (N,)):
+        raise ValueError(f"x [..., {K}] needs wq [N, {K}], scale [N] and b [N]; got {tuple(wq.shape)}, "
+                         f"{tuple(scale.shape)}, {None if b is None else tuple(b.shape)}")
+    M = x.numel() // K if K else 0
+    if (_lib.use_native(x) and 1 <= M <= 16 and K % 16 == 0 and K >= 16 and act in (None, "gelu")
+            and all(t is None or t.dtype == torch.bfloat16 for t in (x, b, residual))
+            and wq.is_cuda and scale.is_cuda and wq.is_contiguous() and scale.dtype == torch.float32
+            and scale.is_contiguous() and not (residual is not None and act is not None)):
+        x2 = x.reshape(M, K).contiguous()
+        r2 = None if residual is None else residual.reshape(M, N).contiguous()
+        b2 = None if b is None else b.contiguous()
+        if _aligned16(x2, wq, scale, b2, r2):
+            from . import _native_linear_decode_fp8
+            y = _native_linear_decode_fp8.linear_small_m_fp8(x2, wq, scale, b2, act, r2)
+            return y.view(*x.shape[:-1], N)
+    return linear(x, (wq.float() * scale[:, None]).to(x.dtype), b, act, residual=residual)
