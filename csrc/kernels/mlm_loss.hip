@@ -32,7 +32,7 @@ __device__ __forceinline__ float block_max256(float m, float* red) {
 template <typename T, int NV>
 __global__ __launch_bounds__(256) void ce_lse_reg_k(const T* __restrict__ logits, long ld, int C,
                                                     const int64_t* __restrict__ labels, long ignore_index,
-                                                    float* __restrict__ lse, float* __restrict__ row_loss) {
+                                                    float* __restrict__ lse, double* __restrict__ row_loss) {
     __shared__ float red[4];
     const long row = blockIdx.x;
     const long lab = labels[row];
@@ -64,9 +64,9 @@ __global__ __launch_bounds__(256) void ce_lse_reg_k(const T* __restrict__ logits
     }
     s = block_sum<256>(s, red);
     if (threadIdx.x == 0) {
-        const float l = m + logf(s);
-        lse[row] = l;
-        row_loss[row] = l - to_f(x[lab]);
+        const float ls = logf(s);
+        lse[row] = m + ls;
+        row_loss[row] = ((double)m + log((double)s)) - (double)to_f(x[lab]);    // fp64, not rounded: see ce_finish_k
     }
 }
 
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void ce_lse_reg_k(const T* __restrict__ logits
 template <typename T>
 __global__ __launch_bounds__(256) void ce_lse_stream_k(const T* __restrict__ logits, long ld, int C,
                                                        const int64_t* __restrict__ labels, long ignore_index,
-                                                       float* __restrict__ lse, float* __restrict__ row_loss) {
+                                                       float* __restrict__ lse, double* __restrict__ row_loss) {
     __shared__ float red[4];
     const long row = blockIdx.x;
     const long lab = labels[row];
@@ -101,21 +101,26 @@ __global__ __launch_bounds__(256) void ce_lse_stream_k(const T* __restrict__ log
     }
     s = block_sum<256>(s, red);
     if (threadIdx.x == 0) {
-        const float l = m + logf(s);
-        lse[row] = l;
-        row_loss[row] = l - to_f(x[lab]);
+        const float ls = logf(s);
+        lse[row] = m + ls;
+        row_loss[row] = ((double)m + log((double)s)) - (double)to_f(x[lab]);    // fp64, not rounded: see ce_finish_k
     }
 }
 
 // Mean over the valid rows in a fixed order (thread t sums rows t, t + 256, ...; then the block tree):
-// the same bits on every run.  No valid row: loss 0 and 1 / n_valid = 0, so the backward writes zeros.
-__global__ __launch_bounds__(256) void ce_finish_k(const float* __restrict__ row_loss,
+// the same bits on every run.  The sum is taken in fp64 and rounded once (as mean_k of elementwise.hip
+// does): in fp32 one saturated row (a loss of ~1e4 among losses of ~8) puts every partial sum at its
+// magnitude and costs the mean its low bits.  The row losses arrive in fp64 for the same reason
+// ((m + log s) - x[label] formed in fp64 from the fp32 m, s and x[label]): rounded to fp32 a loss of 164 is
+// 7.6e-6 off, which a mean over three rows (~56, ulp 3.8e-6) shows as a whole ulp.  No valid row:
+// loss 0 and 1 / n_valid = 0, so the backward writes zeros.
+__global__ __launch_bounds__(256) void ce_finish_k(const double* __restrict__ row_loss,
                                                    const int64_t* __restrict__ labels, long M, int C,
                                                    long ignore_index, float* __restrict__ loss,
                                                    float* __restrict__ inv_n) {
-    __shared__ float red[4];
+    __shared__ double red[256];
     __shared__ int cnt[4];
-    float s = 0.f;
+    double s = 0.0;
     int n = 0;
     for (long r = threadIdx.x; r < M; r += 256) {
         if (row_valid(labels[r], ignore_index, C)) {
@@ -123,14 +128,18 @@ __global__ __launch_bounds__(256) void ce_finish_k(const float* __restrict__ row
             ++n;
         }
     }
-    s = block_sum<256>(s, red);
+    red[threadIdx.x] = s;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
     if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = n;
     __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
     if (threadIdx.x == 0) {
         const int tot = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-        loss[0] = tot > 0 ? s / (float)tot : 0.f;
+        loss[0] = tot > 0 ? (float)(red[0] / (double)tot) : 0.f;
         inv_n[0] = tot > 0 ? 1.f / (float)tot : 0.f;
     }
 }
@@ -222,7 +231,7 @@ inline int grid_for(long n) { return (int)std::max<long>(1, std::min<long>((n + 
 
 template <typename T>
 void launch_lse(const T* x, long M, long ld, int C, const int64_t* labels, long ignore_index, float* lse,
-                float* row_loss, hipStream_t st) {
+                double* row_loss, hipStream_t st) {
     if (C <= 256 * 4 * 8)
         ce_lse_reg_k<T, 4><<<M, 256, 0, st>>>(x, ld, C, labels, ignore_index, lse, row_loss);
     else if (C <= 256 * 16 * 8)
@@ -235,10 +244,10 @@ void launch_lse(const T* x, long M, long ld, int C, const int64_t* labels, long 
 
 DDL_API int ddl_zero(void* p, long nbytes, hipStream_t st);   // elementwise.hip
 
-// lse / row_loss: fp32 [M] workspaces (entries of ignored rows are left unwritten and never read);
+// lse: fp32 [M], row_loss: fp64 [M] workspaces (entries of ignored rows are left unwritten and never read);
 // loss / inv_n: fp32 scalars on the device.
 DDL_API int ddl_ce_lse(int dtype, const void* logits, long M, long ld, int C, const int64_t* labels, long ignore_index,
-                       float* lse, float* row_loss, float* loss, float* inv_n, hipStream_t st) {
+                       float* lse, double* row_loss, float* loss, float* inv_n, hipStream_t st) {
     if (M <= 0 || C <= 0 || ld < C || ld % 8 || ((uintptr_t)logits & 15)) return -1;
     if (dtype == 1) launch_lse<bf16_t>((const bf16_t*)logits, M, ld, C, labels, ignore_index, lse, row_loss, st);
     else launch_lse<float>((const float*)logits, M, ld, C, labels, ignore_index, lse, row_loss, st);

@@ -28,7 +28,7 @@ def _lse(y: torch.Tensor, M: int, ld: int, C: int, labels: torch.Tensor, ignore_
     """(loss, lse [M], 1 / n_valid) of the rows of ``y`` ([M, ld], columns [0, C) valid)."""
     dev = y.device
     lse = torch.empty(M, dtype=torch.float32, device=dev)
-    row = torch.empty(M, dtype=torch.float32, device=dev)
+    row = torch.empty(M, dtype=torch.float64, device=dev)     # row losses, not rounded before the mean
     loss = torch.empty((), dtype=torch.float32, device=dev)
     inv_n = torch.empty(1, dtype=torch.float32, device=dev)
     call("ddl_ce_lse", dcode(y), p(y), M, ld, C, p(labels), ignore_index, p(lse), p(row), p(loss), p(inv_n))

@@ -31,8 +31,10 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, ignore_index: Opti
         from . import _native_mlm
         return _native_mlm.cross_entropy_ignore(logits, labels, ignore_index)
     x = logits if logits.dtype == torch.float64 else logits.float()
-    total = F.cross_entropy(x, labels, ignore_index=ignore_index, reduction="sum")
-    return total / (labels != ignore_index).sum().clamp(min=1)
+    # the row losses are summed in fp64, as ce_finish_k sums them: one saturated row among many
+    # ordinary ones must not cost the mean its low bits
+    rows = F.cross_entropy(x, labels, ignore_index=ignore_index, reduction="none")
+    return (rows.sum(dtype=torch.float64) / (labels != ignore_index).sum().clamp(min=1)).to(x.dtype)
 
 
 def softmax_topk(logits: torch.Tensor, k: int = 5):
