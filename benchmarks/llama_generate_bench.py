@@ -4,7 +4,7 @@ and the decode attention against what the library could compose before it.
 
     python benchmarks/llama_generate_bench.py [--model smollm_135m] [--prompt 128] [--new 128]
                                               [--batches 1,8,16] [--reps 3] [--skip-e2e] [--skip-recompute]
-                                              [--skip-kernels] [--skip-d128] [--fp8]
+                                              [--skip-kernels] [--skip-d128] [--fp8] [--fp8-kv]
 
 End to end (bf16, random weights, greedy, no eos): ``generate`` (prefill + cached decode steps), the same with
 ``use_graph=True`` (the decode step captured once and replayed; the capture is timed once, apart) and the
@@ -34,6 +34,15 @@ call at M = 1 and 16 on Llama-3-8B's four block shapes (device events, the two a
 call on another copy of its weight, copies totalling >= 512 MB per arm; bytes are the weight's: N K (+ 4 N of
 scales) against 2 N K), then ``llama3_8b(num_hidden_layers=4)`` at B = 1 and 16, eager and graph-replayed, with
 and without ``quantize_decode_weights()``.
+
+``--fp8-kv`` runs only the FP8 KV-cache section.  Per call at head dim 128, (H, Hkv) = (32, 8) and (32, 32), B = 1
+and 16, 1023 and 8191 cached keys: ``ops.attention_decode_gqa_fp8`` against ``ops.attention_decode_gqa`` on a bf16
+cache of the same shape against ``attention_decode_gqa_fp8_reference`` (device events, the arms alternating in one
+process, best of 3, every call on another copy of its cache, copies totalling >= 512 MB per arm).  Bytes: 2 (n + 1)
+(128 + 4) per (batch, KV head) against 2 (n + 1) 256.  Only the two B = 16, 8191-key shapes are far above the
+~20 us launch floor; the other six sit at or near it and bound the kernel from above only (``near_floor``).  Then
+``llama3_8b(num_hidden_layers=4)`` at B = 1 and 16, eager and graph-replayed, bf16 against FP8 cache, with and
+without ``quantize_decode_weights()``.
 """
 import argparse
 import json
@@ -264,6 +273,100 @@ def bench_fp8_e2e(dev, args):
     model.clear_decode_weights()
 
 
+def bench_fp8_kv_attention(dev):
+    import torch
+    from databricks_distributed_deep_learning_amd import ops
+    from databricks_distributed_deep_learning_amd.ops.attention import attention_decode_gqa_fp8_reference
+    D = 128
+    for n in (1023, 8191):
+        C = n + 1
+        table = ops.rope_table(C, 5e5, D, dev)
+        for H, Hkv in ((32, 8), (32, 32)):
+            for B in (1, 16):
+                lens = torch.full((B,), n, dtype=torch.int32, device=dev)
+                L16 = min(256, -(-ROTATE_BYTES // (2 * B * Hkv * C * D * 2)))
+                L8 = min(512, -(-ROTATE_BYTES // (2 * B * Hkv * C * (D + 4))))
+                c16 = torch.randn(L16, 2, B, Hkv, C, D, device=dev).bfloat16()
+                c8 = torch.empty(L8, 2, B, Hkv, C, D, dtype=torch.float8_e4m3fn, device=dev)
+                sc = torch.empty(L8, 2, B, Hkv, C, dtype=torch.float32, device=dev)
+                for i in range(L8):
+                    q, s = ops.quantize_fp8_rows(c16[i % L16].view(-1, D))
+                    c8[i], sc[i] = q.view(2, B, Hkv, C, D), s.view(2, B, Hkv, C)
+                proj = torch.randn(B, (H + 2 * Hkv) * D, device=dev).bfloat16()
+
+                def bf16(i):
+                    ops.attention_decode_gqa(proj, table, c16[i % L16, 0], c16[i % L16, 1], lens, H, Hkv, n + 1)
+
+                def fp8(i):
+                    j = i % L8
+                    ops.attention_decode_gqa_fp8(proj, table, c8[j, 0], c8[j, 1], sc[j, 0], sc[j, 1], lens, H, Hkv, n + 1)
+
+                def reference(i):
+                    j = i % L8
+                    attention_decode_gqa_fp8_reference(proj, table, c8[j, 0], c8[j, 1], sc[j, 0], sc[j, 1], lens, H, Hkv,
+                                                       n + 1)
+
+                with torch.no_grad():
+                    _best(bf16, 200, 1), _best(fp8, 200, 1)         # warm-up of both arms
+                    t16 = t8 = float("inf")
+                    for _ in range(3):
+                        t16, t8 = min(t16, _events(bf16, 400)), min(t8, _events(fp8, 400))
+                    t_r = _best(reference, 10 if n > 4096 else 40, 1)
+                nb16, nb8 = d128_bytes(B, Hkv, n), 2 * (n + 1) * (D + 4) * B * Hkv
+                print(json.dumps({"kernel": "attention_decode_gqa_fp8", "B": B, "H": H, "Hkv": Hkv, "G": H // Hkv, "n": n,
+                                  "copies": [L16, L8], "near_floor": not (B == 16 and n == 8191),
+                                  "fp8_us": round(t8, 2), "fp8_GBps": round(nb8 / t8 / 1e3, 1),
+                                  "fp8_share_of_stream": round(nb8 / t8 / 1e6 / STREAM_TBS, 4),
+                                  "bf16_us": round(t16, 2), "bf16_GBps": round(nb16 / t16 / 1e3, 1),
+                                  "bf16_share_of_stream": round(nb16 / t16 / 1e6 / STREAM_TBS, 4),
+                                  "fp8_reference_us": round(t_r, 2), "fp8_over_bf16": round(t8 / t16, 3),
+                                  "fp8_faster": bool(t8 < t16)}), flush=True)
+                del c16, c8, sc
+
+
+def bench_fp8_kv_e2e(dev, args):
+    """``llama3_8b(num_hidden_layers=4)``, B = 1 and 16: ``generate`` eager and graph-replayed on a bf16 and on an
+    FP8 cache, with the bf16 weights and with ``quantize_decode_weights()``; each round runs all eight arms (a
+    switch of weights or cache rebuilds the session: one untimed graph call first)."""
+    import torch
+    from databricks_distributed_deep_learning_amd.models import cast_params, llama3_8b
+    torch.manual_seed(0)
+    with torch.device(dev):
+        model = llama3_8b(num_hidden_layers=4).eval()
+    cast_params(model, torch.bfloat16)
+    for B in (1, 16):
+        ids = torch.randint(0, model.config.vocab_size, (B, args.prompt), device=dev)
+
+        def timed(**kw):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            out = model.generate(ids, max_new_tokens=args.new, **kw)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t, out
+        times, outs = {}, {}
+        for rnd in range(args.reps + 1):        # (the first round warms up)
+            for w in ("w16", "w8"):
+                model.quantize_decode_weights() if w == "w8" else model.clear_decode_weights()
+                for kv in ("kv16", "kv8"):
+                    kw = {"kv_cache_dtype": "fp8"} if kv == "kv8" else {}
+                    timed(use_graph=True, **kw)         # captures the session for these weights and this cache
+                    for arm, more in (("cached", {}), ("graph", {"use_graph": True})):
+                        t, outs[w, kv, arm] = timed(**kw, **more)
+                        if rnd:
+                            times.setdefault((w, kv, arm), []).append(t)
+        tps = {k: B * args.new / min(v) for k, v in times.items()}
+        print(json.dumps({"e2e": "llama3_8b(num_hidden_layers=4)", "B": B, "prompt": args.prompt, "new": args.new,
+                          **{"_".join(k) + "_tokens_per_s": round(v, 1) for k, v in tps.items()},
+                          **{f"kv8_speedup_{w}_{arm}": round(tps[w, "kv8", arm] / tps[w, "kv16", arm], 3)
+                             for w in ("w16", "w8") for arm in ("cached", "graph")},
+                          "kv8_graph_token_agreement_with_cached":
+                              round((outs["w16", "kv8", "cached"] == outs["w16", "kv8", "graph"]).float().mean().item(), 4),
+                          "kv8_token_agreement_with_kv16":
+                              round((outs["w16", "kv8", "cached"] == outs["w16", "kv16", "cached"]).float().mean().item(),
+                                    4)}), flush=True)
+    model.clear_decode_weights()
+
+
 def bench_e2e(dev, args):
     import torch
     from databricks_distributed_deep_learning_amd import models
@@ -344,6 +447,7 @@ def main() -> int:
     ap.add_argument("--skip-recompute", action="store_true", help="end to end: the cached and graph arms only")
     ap.add_argument("--skip-d128", action="store_true", help="no head-dim-128 section (per call and llama3_8b)")
     ap.add_argument("--fp8", action="store_true", help="only the FP8 decode-weight section (per call and llama3_8b)")
+    ap.add_argument("--fp8-kv", action="store_true", help="only the FP8 KV-cache section (per call and llama3_8b)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -352,6 +456,10 @@ def main() -> int:
     if args.fp8:
         bench_fp8_linears(dev)
         bench_fp8_e2e(dev, args)
+        return 0
+    if args.fp8_kv:
+        bench_fp8_kv_attention(dev)
+        bench_fp8_kv_e2e(dev, args)
         return 0
     if not args.skip_e2e:
         bench_e2e(dev, args)

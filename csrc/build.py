@@ -66,6 +66,7 @@ _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA["attn_decode_d128.hip"] = _NO_PK_F32
 EXTRA["attn_extend_d128.hip"] = _NO_PK_F32
 EXTRA["linear_decode_fp8.hip"] = _NO_PK_F32
+EXTRA["attn_decode_d128_fp8.hip"] = _NO_PK_F32
 
 
 # Sources whose code decides which GEMM kernel runs fastest for a shape: their hash keys the committed

@@ -28,26 +28,28 @@ def round_capacity(need: int, n_positions: int) -> int:
     return min((need + 127) // 128 * 128, n_positions)
 
 
-def _key(model, batch: int, capacity: int, graph: bool, ext: bool = False):
+def _key(model, batch: int, capacity: int, graph: bool, ext: bool = False, kv_fp8: bool = False):
     w = model._session_weight()
     # (a model may name further tensors its step reads, such as quantised decode weights, in _session_tensors)
     more = getattr(model, "_session_tensors", lambda: ())()
     return (batch, capacity, w.device, w.dtype, graph, ext, tuple(p.data_ptr() for p in model.parameters()),
-            tuple(t.data_ptr() for t in more))
+            tuple(t.data_ptr() for t in more), kv_fp8)
 
 
-def session_for(model, batch: int, capacity: int, graph: bool, ext: bool = False) -> "DecodeSession":
+def session_for(model, batch: int, capacity: int, graph: bool, ext: bool = False,
+                kv_fp8: bool = False) -> "DecodeSession":
     """The model's session for this shape: rebuilt when the batch, the capacity, the device, the dtype or
     the address of any parameter (or of any tensor of the model's ``_session_tensors()``) baked into the captured
     step has changed.  ``ext``: a session whose step
     also serves top-p, min-p and a repetition penalty (another launch in the captured step, so part of the
-    key); without it the step is the one it always was."""
-    key = _key(model, batch, capacity, graph, ext)
+    key); without it the step is the one it always was.  ``kv_fp8``: the session's cache is an FP8 one (models
+    that have one: ``_session_cache(..., fp8=True)``); part of the key, so a change rebuilds the session."""
+    key = _key(model, batch, capacity, graph, ext, kv_fp8)
     s = _sessions.get(model)
     if s is None or s.key != key:
         s = None
         _sessions.pop(model, None)          # (frees the old session's cache before the new one is allocated)
-        s = _sessions[model] = DecodeSession(model, batch, capacity, graph, key, ext)
+        s = _sessions[model] = DecodeSession(model, batch, capacity, graph, key, ext, kv_fp8)
     return s
 
 
@@ -58,12 +60,14 @@ def current_session(model):
 class DecodeSession:
     WARMUP = 2
 
-    def __init__(self, model, batch: int, capacity: int, graph: bool, key=None, ext: bool = False):
+    def __init__(self, model, batch: int, capacity: int, graph: bool, key=None, ext: bool = False,
+                 kv_fp8: bool = False):
         dev = model._session_weight().device
         self.key = key
         self._model = weakref.ref(model)
         self.batch, self.capacity = batch, capacity
-        self.cache = model._session_cache(batch, capacity, dev)
+        self.cache = (model._session_cache(batch, capacity, dev, fp8=True) if kv_fp8
+                      else model._session_cache(batch, capacity, dev))
         self.tok_cur = torch.zeros(batch, dtype=torch.int64, device=dev)
         self.done = torch.zeros(batch, dtype=torch.bool, device=dev)
         self.step = torch.zeros(batch, dtype=torch.int32, device=dev)

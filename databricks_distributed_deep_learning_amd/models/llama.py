@@ -32,6 +32,11 @@ its group and appends.  ``generate(use_graph=True)`` runs the step from a decode
 there is no position embedding to add); ``generate(prefix=...)`` starts from a copy of a prefilled cache and
 ``prefill(chunk=...)`` consumes a prompt through ``extend`` in chunks.
 
+An FP8 KV cache (``LlamaKVCache.allocate(fp8=True)``, ``generate(kv_cache_dtype="fp8")``): e4m3 bytes with one fp32
+scale per cached row, half the bytes a decode step streams and half the cache's memory.  ``prefill``, ``decode`` and
+``extend`` then call ``ops.kv_cache_fill_gqa_fp8``, ``ops.attention_decode_gqa_fp8`` (both native at head dimension
+128) and ``ops.attention_extend_gqa_fp8`` (a torch composition); any other cache runs exactly what it ran before.
+
 Not covered: ``generate(prefill_chunk=...)`` (chunked prompt consumption is on ``prefill``), ``rope_scaling``,
 sliding-window attention, biased projections.
 """
@@ -79,22 +84,33 @@ class RMSNorm(nn.Module):
 class LlamaKVCache:
     """Rotated keys and values of every layer, ``data [L, 2, B, Hkv, C, D]`` (C: capacity in positions), the
     valid length of each batch row on the device (``lens``, int32 ``[B]``) and ``max_len``, the host's upper
-    bound on ``lens`` -- what sizes the decode launches, so no step reads ``lens`` back."""
+    bound on ``lens`` -- what sizes the decode launches, so no step reads ``lens`` back.
 
-    def __init__(self, data: torch.Tensor, lens: torch.Tensor):
-        self.data, self.lens = data, lens
+    An FP8 cache (``allocate(fp8=True)``) holds ``data`` as ``torch.float8_e4m3fn`` and ``scales [L, 2, B, Hkv, C]``
+    fp32, one per cached row (``ops.attention_decode_gqa_fp8``'s format): half the bytes a decode step streams and
+    half the memory.  ``scales`` is None on any other cache."""
+
+    def __init__(self, data: torch.Tensor, lens: torch.Tensor, scales: torch.Tensor = None):
+        self.data, self.lens, self.scales = data, lens, scales
         self.capacity = data.shape[4]
         self.max_len = 0
 
     @classmethod
     def allocate(cls, model: "LlamaForCausalLM", batch: int, capacity: int, device=None,
-                 dtype=None) -> "LlamaKVCache":
+                 dtype=None, fp8: bool = False) -> "LlamaKVCache":
         c = model.config
         if not 1 <= capacity <= c.max_position_embeddings:
             raise ValueError(f"capacity {capacity} must be in 1 .. max_position_embeddings "
                              f"({c.max_position_embeddings})")
         w = model.embed_tokens.weight
         device = w.device if device is None else device
+        if fp8:
+            if dtype not in (None, torch.float8_e4m3fn):
+                raise ValueError(f"an fp8 cache is torch.float8_e4m3fn, got dtype={dtype}")
+            shape = (c.num_hidden_layers, 2, batch, c.num_key_value_heads, capacity)
+            data = torch.empty(*shape, c.hidden_size // c.num_attention_heads, dtype=torch.uint8, device=device)
+            return cls(data.view(torch.float8_e4m3fn), torch.zeros(batch, dtype=torch.int32, device=device),
+                       torch.empty(shape, dtype=torch.float32, device=device))
         data = torch.empty(c.num_hidden_layers, 2, batch, c.num_key_value_heads, capacity,
                            c.hidden_size // c.num_attention_heads, dtype=w.dtype if dtype is None else dtype,
                            device=device)
@@ -106,12 +122,19 @@ class LlamaKVCache:
     def v(self, layer: int) -> torch.Tensor:
         return self.data[layer, 1]
 
+    def k_scale(self, layer: int) -> torch.Tensor:
+        return self.scales[layer, 0]
+
+    def v_scale(self, layer: int) -> torch.Tensor:
+        return self.scales[layer, 1]
+
     def copy_prefix_(self, src: "LlamaKVCache") -> "LlamaKVCache":
         """Start this cache from ``src``'s contents: positions ``< src.max_len`` of every layer, ``lens`` and
         ``max_len``.  ``src`` has this cache's batch or batch 1 (one prefix shared by every row), its dtype and
         its device (nothing is converted or moved silently); it is only read.  Rows of ``src`` may have unequal
         ``lens``: ``src.max_len``, their bound, is what is copied and what ``generate`` counts against
-        ``max_position_embeddings``."""
+        ``max_position_embeddings``.  An FP8 cache starts from an FP8 prefix only (bytes and scales are copied;
+        nothing is quantised or dequantised here)."""
         L, _, B, H, C, D = self.data.shape
         Ls, _, Bs, Hs, _, Ds = src.data.shape
         if (Ls, Hs, Ds) != (L, H, D):
@@ -124,7 +147,11 @@ class LlamaKVCache:
         if src.max_len > C:
             raise ValueError(f"prefix length {src.max_len} exceeds the cache capacity {C}")
         n = src.max_len
-        self.data[:, :, :, :, :n].copy_(src.data[:, :, :, :, :n])
+        if self.scales is not None:
+            self.data.view(torch.uint8)[:, :, :, :, :n].copy_(src.data.view(torch.uint8)[:, :, :, :, :n])
+            self.scales[:, :, :, :, :n].copy_(src.scales[:, :, :, :, :n])
+        else:
+            self.data[:, :, :, :, :n].copy_(src.data[:, :, :, :, :n])
         self.lens.copy_(src.lens)
         self.max_len = n
         return self
@@ -178,7 +205,11 @@ class LlamaBlock(nn.Module):
     def prefill(self, h, table, mask, cache: LlamaKVCache, layer: int):
         """The inference forward that also copies this layer's rotated keys and its values into the cache."""
         qkv = ops.rope_qkv(self.qkv(self.input_layernorm(h)), table, self.num_heads, self.num_kv_heads)
-        ops.kv_cache_fill_gqa(qkv, cache.k(layer), cache.v(layer), self.num_heads, self.num_kv_heads)
+        if cache.scales is not None:
+            ops.kv_cache_fill_gqa_fp8(qkv, cache.k(layer), cache.v(layer), cache.k_scale(layer), cache.v_scale(layer),
+                                      self.num_heads, self.num_kv_heads)
+        else:
+            ops.kv_cache_fill_gqa(qkv, cache.k(layer), cache.v(layer), self.num_heads, self.num_kv_heads)
         h = self.o_proj(ops.attention(qkv, self.num_heads, mask, 0.0, False, causal=True), residual=h)
         return self.down_proj(ops.swiglu(self.gate_up(self.post_attention_layernorm(h))), residual=h)
 
@@ -187,8 +218,14 @@ class LlamaBlock(nn.Module):
         its value).  ``len_bound``: the bound on ``lens + 1`` that sizes the attention launch (default
         ``max_len + 1``)."""
         qkv = self._lin("qkv", self.input_layernorm(h_new))
-        ctx = ops.attention_decode_gqa(qkv, table, cache.k(layer), cache.v(layer), cache.lens, self.num_heads,
-                                       self.num_kv_heads, cache.max_len + 1 if len_bound is None else len_bound)
+        bound = cache.max_len + 1 if len_bound is None else len_bound
+        if cache.scales is not None:
+            ctx = ops.attention_decode_gqa_fp8(qkv, table, cache.k(layer), cache.v(layer), cache.k_scale(layer),
+                                               cache.v_scale(layer), cache.lens, self.num_heads, self.num_kv_heads,
+                                               bound)
+        else:
+            ctx = ops.attention_decode_gqa(qkv, table, cache.k(layer), cache.v(layer), cache.lens, self.num_heads,
+                                           self.num_kv_heads, bound)
         return self._small_m_tail(ctx, h_new)
 
     def _small_m_tail(self, ctx, h):
@@ -206,9 +243,14 @@ class LlamaBlock(nn.Module):
         small = h.shape[0] * h.shape[1] <= 16
         y = self.input_layernorm(h)
         qkv = self._lin("qkv", y) if small else self.qkv(y)
-        ctx = ops.attention_extend_gqa(qkv, table, cache.k(layer), cache.v(layer), cache.lens, self.num_heads,
-                                       self.num_kv_heads, cache.max_len if len_bound is None else len_bound,
-                                       new_lens)
+        bound = cache.max_len if len_bound is None else len_bound
+        if cache.scales is not None:
+            ctx = ops.attention_extend_gqa_fp8(qkv, table, cache.k(layer), cache.v(layer), cache.k_scale(layer),
+                                               cache.v_scale(layer), cache.lens, self.num_heads, self.num_kv_heads,
+                                               bound, new_lens)
+        else:
+            ctx = ops.attention_extend_gqa(qkv, table, cache.k(layer), cache.v(layer), cache.lens, self.num_heads,
+                                           self.num_kv_heads, bound, new_lens)
         if small:
             return self._small_m_tail(ctx, h)
         h = self.o_proj(ctx, residual=h)
@@ -435,7 +477,7 @@ class LlamaForCausalLM(nn.Module):
     def generate(self, input_ids, attention_mask=None, max_new_tokens: int = 20, do_sample: bool = False,
                  temperature: float = 1.0, top_k=None, eos_token_id=None, pad_token_id=None, generator=None,
                  use_graph: bool = False, prefix: LlamaKVCache = None, top_p=None, min_p=None,
-                 repetition_penalty=None):
+                 repetition_penalty=None, kv_cache_dtype=None):
         """Greedy (argmax) or sampled (temperature, then top-k, then multinomial) continuation of
         ``input_ids [B, S_in]`` -> ``[B, S_in + n_new]``: ``GPT2LMHeadModel.generate``'s contract.  Each row
         as given, then its generated tokens, with ``pad_token_id`` (default ``eos_token_id``) after the first
@@ -462,7 +504,16 @@ class LlamaForCausalLM(nn.Module):
         ``prefix``: a ``LlamaKVCache`` (of batch B, or of batch 1 and shared by every row) that already holds
         the tokens before ``input_ids``, e.g. a system prompt prefilled once: it is copied into this call's
         own cache (the session's, under ``use_graph``), never modified, and the prompt is consumed by
-        ``extend`` on top of it, so row b's prompt starts at rotary position ``prefix.lens[b]``."""
+        ``extend`` on top of it, so row b's prompt starts at rotary position ``prefix.lens[b]``.
+
+        ``kv_cache_dtype="fp8"``: this call's cache (the session's, under ``use_graph``) is an FP8 one
+        (``LlamaKVCache.allocate(fp8=True)``): half the K / V bytes a decode step streams and half the cache's
+        memory, with keys and values rounded to e4m3 with a per-row scale; a ``prefix`` must then be an FP8
+        cache too.  Native at head dimension 128; other head dimensions run the reference ops.  None: the
+        cache has the parameters' dtype, as ever."""
+        if kv_cache_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_cache_dtype must be None or 'fp8', got {kv_cache_dtype!r}")
+        fp8 = kv_cache_dtype == "fp8"
         B, S_in = input_ids.shape
         G.check_sampling(max_new_tokens, do_sample, temperature, top_k, top_p, min_p, repetition_penalty)
         ext = top_p is not None or min_p is not None or repetition_penalty is not None
@@ -482,13 +533,13 @@ class LlamaForCausalLM(nn.Module):
             if use_graph:
                 from ._decode_graph import round_capacity, session_for
                 sess = session_for(self, B, round_capacity(need, n_pos),
-                                   G.use_graph_for(self.embed_tokens.weight), ext)
+                                   G.use_graph_for(self.embed_tokens.weight), ext, kv_fp8=fp8)
                 new = G.session_loop(sess, lambda cache: self._consume_prompt(ids, cnt, cache, prefix), B, dev,
                                      max_new_tokens, do_sample, temperature, top_k, eos_token_id, pad_token_id,
                                      generator, top_p, min_p, repetition_penalty, ids if ext else None,
                                      cnt if ext else None)
             else:
-                cache = LlamaKVCache.allocate(self, B, need, dev)
+                cache = LlamaKVCache.allocate(self, B, need, dev, fp8=fp8)
                 new = G.token_loop(self._consume_prompt(ids, cnt, cache, prefix),
                                    lambda tok: self.decode_step(tok, cache), max_new_tokens, do_sample,
                                    temperature, top_k, eos_token_id, pad_token_id, generator, top_p, min_p,
@@ -511,8 +562,8 @@ class LlamaForCausalLM(nn.Module):
         """Tensors the captured step reads that are not parameters: the FP8 decode weights."""
         return [t for blk in self.layers if blk._fp8 is not None for pair in blk._fp8.values() for t in pair]
 
-    def _session_cache(self, batch, capacity, device):
-        return LlamaKVCache.allocate(self, batch, capacity, device)
+    def _session_cache(self, batch, capacity, device, fp8: bool = False):
+        return LlamaKVCache.allocate(self, batch, capacity, device, fp8=fp8)
 
     def _session_logits(self, tok_cur, cache: LlamaKVCache):
         return self._step_logits(tok_cur, cache, cache.capacity)

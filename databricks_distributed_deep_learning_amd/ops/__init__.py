@@ -18,6 +18,7 @@ from .activation import gelu, dropout, relu  # noqa: F401
 from .attention import attention, attention_decode, attention_extend, kv_cache_fill  # noqa: F401
 from .attention import doc_bounds  # noqa: F401
 from .attention import attention_decode_gqa, attention_extend_gqa, kv_cache_fill_gqa  # noqa: F401
+from .attention import attention_decode_gqa_fp8, attention_extend_gqa_fp8, kv_cache_fill_gqa_fp8  # noqa: F401
 from .decode import decode_embed, next_token, next_token_params  # noqa: F401
 from .loss import cross_entropy, softmax_topk  # noqa: F401
 from .pool import max_pool2d, global_avg_pool  # noqa: F401

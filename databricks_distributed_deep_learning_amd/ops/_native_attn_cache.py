@@ -44,6 +44,9 @@ _lib.register({
     "ddl_attn_extend_gqa_d128_supported": [I, I],
     "ddl_attn_extend_gqa_d128_tile": [I, I, I],
     "ddl_attn_extend_gqa_d128": [P, P, P, P, P, P, P, I, I, I, I, I, I, L, CF, P],
+    "ddl_attn_decode_gqa_d128_fp8_supported": [I, I, I],
+    "ddl_attn_decode_gqa_d128_fp8": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, L, CF, P],
+    "ddl_kv_cache_fill_gqa_d128_fp8": [P, P, P, P, P, I, I, I, I, I, P],
 })
 
 _SCALE = 1.0 / math.sqrt(64)
@@ -92,6 +95,12 @@ def supported_extend(num_heads: int, num_kv_heads: int, head_dim: int = 64) -> b
     if head_dim == 64:
         return supported(num_heads, num_kv_heads)
     return bool(head_dim == 128 and _lib.fn("ddl_attn_extend_gqa_d128_supported")(num_heads, num_kv_heads))
+
+
+def supported_decode_fp8(num_heads: int, num_kv_heads: int, head_dim: int = 128) -> bool:
+    """What ``attention_decode_gqa_fp8`` and ``kv_cache_fill_gqa_fp8`` take natively: head dim 128 and the bf16
+    kernel's group sizes (csrc/kernels/attn_decode_d128_fp8.hip)."""
+    return bool(_lib.fn("ddl_attn_decode_gqa_d128_fp8_supported")(num_heads, num_kv_heads, head_dim))
 
 
 def tile(T: int, num_heads: int, num_kv_heads: int, head_dim: int = 64) -> int:
@@ -191,3 +200,23 @@ def kv_cache_fill_gqa(packed, cache_k, cache_v, num_heads, num_kv_heads):
     packed = packed.contiguous()
     _lib.call("ddl_kv_cache_fill_gqa" if D == 64 else "ddl_kv_cache_fill_gqa_d128", packed.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(), B, S, num_heads,
               num_kv_heads, cache_k.shape[2])
+
+
+def attention_decode_gqa_fp8(qkv_new, table, cache_k, cache_v, scale_k, scale_v, lens, num_heads, num_kv_heads,
+                             max_len):
+    """The caller (``ops.attention``) has checked the shapes, dtypes and contiguity of the four cache tensors."""
+    B, H, Hkv = qkv_new.shape[0], num_heads, num_kv_heads
+    qkv_new, table = qkv_new.contiguous(), table.contiguous()
+    out = torch.empty(B, H * 128, dtype=qkv_new.dtype, device=qkv_new.device)
+    ws = _workspace("ddl_attn_decode_gqa_ws_hd", qkv_new.device, B, H, Hkv, max_len, 128)    # the bf16 kernel's plan
+    _lib.call("ddl_attn_decode_gqa_d128_fp8", qkv_new.data_ptr(), table.data_ptr(), cache_k.data_ptr(),
+              cache_v.data_ptr(), scale_k.data_ptr(), scale_v.data_ptr(), lens.data_ptr(), out.data_ptr(), _lib.p(ws),
+              B, H, Hkv, cache_k.shape[2], max_len, table.shape[0], 1.0 / math.sqrt(128))
+    return out
+
+
+def kv_cache_fill_gqa_fp8(packed, cache_k, cache_v, scale_k, scale_v, num_heads, num_kv_heads):
+    B, S, _ = packed.shape
+    packed = packed.contiguous()
+    _lib.call("ddl_kv_cache_fill_gqa_d128_fp8", packed.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(),
+              scale_k.data_ptr(), scale_v.data_ptr(), B, S, num_heads, num_kv_heads, cache_k.shape[2])

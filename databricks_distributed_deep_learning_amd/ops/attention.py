@@ -501,3 +501,166 @@ def attention_extend_gqa(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: to
                                           new_lens)
     return attention_extend_gqa_reference(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len,
                                           new_lens)
+
+
+# ------------------------------------------------------------------ grouped-query decode on an FP8 KV cache
+# The grouped-query cache above at one byte per element: cache_k / cache_v [B, Hkv, C, D] torch.float8_e4m3fn
+# (or uint8 holding those bits) and scale_k / scale_v [B, Hkv, C] fp32, contiguous; element (b, h, j, i) is
+# float(byte) * scale[b, h, j].  A row is quantised by ops.quantize_fp8_rows applied to that row of D: keys after
+# the rotation and its one rounding to the input dtype, values from the projection.  The attention sees the
+# DEQUANTISED row, also for the token being appended, so every later step sees a key exactly as the step that
+# wrote it did.  Everything else -- qkv_new, table, lens, max_len, the dead-row rule -- is the bf16 cache's.
+def _fp8_cache_views(cache_k, cache_v, scale_k, scale_v):
+    """-> the byte caches as ``torch.float8_e4m3fn`` after the checks the bf16 guards do not make."""
+    views = []
+    for name, t in (("cache_k", cache_k), ("cache_v", cache_v)):
+        if t.dtype == torch.uint8:
+            t = t.view(torch.float8_e4m3fn)
+        if t.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"{name} must be torch.float8_e4m3fn (or uint8 holding its bits), got {t.dtype}")
+        views.append(t)
+    for name, s in (("scale_k", scale_k), ("scale_v", scale_v)):
+        if s.dtype != torch.float32 or s.shape != cache_k.shape[:3] or not s.is_contiguous() \
+                or s.device != cache_k.device:
+            raise ValueError(f"{name} must be a contiguous fp32 {tuple(cache_k.shape[:3])} tensor on the cache's "
+                             f"device, got {s.dtype} {tuple(s.shape)}")
+    _no_autograd("an fp8 KV cache op", scale_k, scale_v)
+    return views
+
+
+def _quantize_rows(x):
+    """``x [..., D]`` -> (bytes as uint8 ``[..., D]``, fp32 scales ``[...]``) by ``quantize_fp8_rows``.  On a GPU
+    tensor torch forms ``amax / 448`` through a rounded reciprocal, so a scale (and with it a byte) can sit one ulp
+    from the format's true division, which the CPU and the native kernels compute: rows written here on the GPU
+    (the references, ``attention_extend_gqa_fp8``) are then not bit-identical to natively written ones.  A row is
+    always read back with the scale it was stored with."""
+    from .linear import quantize_fp8_rows
+    q, s = quantize_fp8_rows(x.reshape(-1, x.shape[-1]))
+    return q.view(torch.uint8).view(x.shape), s.view(x.shape[:-1])
+
+
+def _dequantize(cache, scale, L, ct):
+    return cache[:, :, :L].float().to(ct) * scale[:, :, :L, None].to(ct)
+
+
+def _native_fp8(qkv, cache_k, cache_v, scale_k, scale_v, D, num_heads, num_kv_heads, *more):
+    if not (_lib.use_native(qkv, cache_k, cache_v, scale_k, scale_v, *more) and qkv.dtype == torch.bfloat16
+            and D == 128 and cache_k.data_ptr() % 8 == 0 and cache_v.data_ptr() % 8 == 0):
+        return None
+    from . import _native_attn_cache as N
+    return N if N.supported_decode_fp8(num_heads, num_kv_heads, D) else None
+
+
+def attention_decode_gqa_fp8_reference(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: torch.Tensor,
+                                       cache_v: torch.Tensor, scale_k: torch.Tensor, scale_v: torch.Tensor,
+                                       lens: torch.Tensor, num_heads: int, num_kv_heads: int,
+                                       max_len: int) -> torch.Tensor:
+    cache_k, cache_v = _fp8_cache_views(cache_k, cache_v, scale_k, scale_v)
+    D = _decode_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len)
+    B, H, Hkv, half = qkv_new.shape[0], num_heads, num_kv_heads, D // 2
+    G = H // Hkv
+    dev = qkv_new.device
+    ct = torch.float64 if qkv_new.dtype == torch.float64 else torch.float32
+    n = lens.long()
+    x = qkv_new.to(ct).view(B, H + 2 * Hkv, D)
+    row = table[n].to(ct)                                                              # [B, D]
+    cos, sin = row[:, None, :half], row[:, None, half:]
+
+    def rot(t):
+        a, b = t[..., :half], t[..., half:]
+        return torch.cat([a * cos - b * sin, b * cos + a * sin], -1)
+
+    # rounded once to the input dtype, then the new key and value quantised: the attention reads them back
+    q = rot(x[:, :H]).to(qkv_new.dtype)
+    bi = torch.arange(B, device=dev)
+    for cache, scale, new in ((cache_k, scale_k, rot(x[:, H:H + Hkv]).to(qkv_new.dtype)),
+                              (cache_v, scale_v, qkv_new.view(B, H + 2 * Hkv, D)[:, H + Hkv:])):
+        cache.view(torch.uint8)[bi, :, n], scale[bi, :, n] = _quantize_rows(new)
+    live = torch.arange(max_len, device=dev).view(1, 1, 1, max_len) <= n.view(B, 1, 1, 1)
+    kk, vv = _dequantize(cache_k, scale_k, max_len, ct), _dequantize(cache_v, scale_v, max_len, ct)
+    s = q.to(ct).view(B, Hkv, G, D) @ kk.transpose(-1, -2) / math.sqrt(D)              # [B, Hkv, G, L]
+    # selects, not multiplies: a dead position may hold any bit pattern, bytes and scales
+    p = torch.softmax(torch.where(live, s, torch.full_like(s, float("-inf"))), -1)
+    vv = torch.where(live.squeeze(1).unsqueeze(-1), vv, torch.zeros_like(vv))
+    return (p @ vv).reshape(B, H * D).to(qkv_new.dtype)
+
+
+def attention_decode_gqa_fp8(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
+                             scale_k: torch.Tensor, scale_v: torch.Tensor, lens: torch.Tensor, num_heads: int,
+                             num_kv_heads: int, max_len: int) -> torch.Tensor:
+    """``attention_decode_gqa`` on an FP8 cache (e4m3 bytes with one fp32 scale per cached row): the new token's
+    rotation, its quantisation by ``quantize_fp8_rows`` and the append, attention over the dequantised rows;
+    returns ``[B, H·D]``.  Native at head dimension 128 (csrc/kernels/attn_decode_d128_fp8.hip: bf16 ``qkv_new``,
+    fp32 table, G in 1, 2, 3, 4, 8, 8-byte-aligned caches): half the K / V bytes of the bf16 call.  Everything
+    else runs the reference -- head dimension 64 with an fp8 cache too: there is no native kernel for it.  The
+    references quantise with torch's ``quantize_fp8_rows``: on the GPU, one ulp of scale from the native kernels'
+    true division in places (``_quantize_rows``)."""
+    ck, cv = _fp8_cache_views(cache_k, cache_v, scale_k, scale_v)
+    D = _decode_gqa_guard(qkv_new, table, ck, cv, lens, num_heads, num_kv_heads, max_len)
+    N = None
+    if table.dtype == torch.float32:
+        N = _native_fp8(qkv_new, ck, cv, scale_k, scale_v, D, num_heads, num_kv_heads, table, lens)
+    if N is not None:
+        return N.attention_decode_gqa_fp8(qkv_new, table, ck, cv, scale_k, scale_v, lens, num_heads, num_kv_heads,
+                                          max_len)
+    return attention_decode_gqa_fp8_reference(qkv_new, table, ck, cv, scale_k, scale_v, lens, num_heads,
+                                              num_kv_heads, max_len)
+
+
+def kv_cache_fill_gqa_fp8_reference(packed: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
+                                    scale_k: torch.Tensor, scale_v: torch.Tensor, num_heads: int,
+                                    num_kv_heads: int) -> None:
+    cache_k, cache_v = _fp8_cache_views(cache_k, cache_v, scale_k, scale_v)
+    D = _fill_gqa_guard(packed, cache_k, cache_v, num_heads, num_kv_heads)
+    B, S, _ = packed.shape
+    G = num_heads // num_kv_heads
+    _, k, v = packed.view(B, S, 3, num_heads, D)[:, :, :, ::G].permute(2, 0, 3, 1, 4).unbind(0)
+    for cache, scale, new in ((cache_k, scale_k, k), (cache_v, scale_v, v)):
+        cache.view(torch.uint8)[:, :, :S], scale[:, :, :S] = _quantize_rows(new)
+
+
+def kv_cache_fill_gqa_fp8(packed: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor, scale_k: torch.Tensor,
+                          scale_v: torch.Tensor, num_heads: int, num_kv_heads: int) -> None:
+    """``kv_cache_fill_gqa`` into an FP8 cache: the first slot of every group of ``rope_qkv``'s packed
+    ``[B, S, 3·H·D]``, each row quantised by ``quantize_fp8_rows``, to positions 0..S-1 of the two byte caches
+    and the two scale tensors (rows past a sequence's own length too).  Native at head dimension 128, bf16."""
+    ck, cv = _fp8_cache_views(cache_k, cache_v, scale_k, scale_v)
+    D = _fill_gqa_guard(packed, ck, cv, num_heads, num_kv_heads)
+    N = _native_fp8(packed, ck, cv, scale_k, scale_v, D, num_heads, num_kv_heads)
+    if N is not None:
+        return N.kv_cache_fill_gqa_fp8(packed, ck, cv, scale_k, scale_v, num_heads, num_kv_heads)
+    return kv_cache_fill_gqa_fp8_reference(packed, ck, cv, scale_k, scale_v, num_heads, num_kv_heads)
+
+
+def attention_extend_gqa_fp8(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
+                             scale_k: torch.Tensor, scale_v: torch.Tensor, lens: torch.Tensor, num_heads: int,
+                             num_kv_heads: int, max_len: int, new_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``attention_extend_gqa`` on an FP8 cache, as a composition with no kernel of its own: the first
+    ``max_len`` positions are dequantised into a scratch cache of ``max_len + T`` positions in ``qkv_new``'s
+    dtype, ``attention_extend_gqa`` runs on it (native where that op is), and the rows it appended are quantised
+    back with ``quantize_fp8_rows``.  Inside this one call the chunk's own keys and values are therefore seen
+    UNQUANTISED by the chunk's queries; every later call sees them quantised.  On the GPU the write-back is torch's
+    ``quantize_fp8_rows``, whose scales can sit one ulp from the true division of the native fill and decode
+    kernels (``_quantize_rows``): the rows are self-consistent, not bit-identical to natively written ones.
+    Nothing syncs."""
+    ck, cv = _fp8_cache_views(cache_k, cache_v, scale_k, scale_v)
+    _extend_gqa_guard(qkv_new, table, ck, cv, lens, num_heads, num_kv_heads, max_len, new_lens)
+    B, T, dev = qkv_new.shape[0], qkv_new.shape[1], qkv_new.device
+    tmp = []
+    for cache, scale in ((ck, scale_k), (cv, scale_v)):
+        t = torch.zeros(B, num_kv_heads, max_len + T, ck.shape[3], dtype=qkv_new.dtype, device=dev)
+        t[:, :, :max_len] = _dequantize(cache, scale, max_len, torch.float32)
+        tmp.append(t)
+    out = attention_extend_gqa(qkv_new, table, tmp[0], tmp[1], lens, num_heads, num_kv_heads, max_len, new_lens)
+    # chunk position i < t of row b went to scratch position n + i: those rows, quantised, to the cache
+    n = lens.long().clamp(0, max_len)
+    t = torch.full_like(n, T) if new_lens is None else new_lens.long().clamp(1, T)
+    i = torch.arange(T, device=dev)
+    real = (i.view(1, T) < t.view(B, 1)).view(B, T, 1)
+    bi, pos = torch.arange(B, device=dev).view(B, 1), n.view(B, 1) + i.view(1, T)
+    for cache, scale, src in ((ck, scale_k, tmp[0]), (cv, scale_v, tmp[1])):
+        q, s = _quantize_rows(src[bi, :, pos])                                         # [B, T, Hkv, D], [B, T, Hkv]
+        c8 = cache.view(torch.uint8)
+        c8[bi, :, pos] = torch.where(real.unsqueeze(-1), q, c8[bi, :, pos])
+        scale[bi, :, pos] = torch.where(real, s, scale[bi, :, pos])
+    return out
