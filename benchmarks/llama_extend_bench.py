@@ -27,6 +27,14 @@ best of ``--reps`` runs after one warm-up run of each arm, the arms alternating 
     both from the shapes; ``floor_bound`` marks a call time within 1.5x of the ~20 us enqueue floor, which bounds
     the kernel from above and does not measure it.
 (e) (a) for ``llama3_8b(num_hidden_layers=4)``.
+
+``--fp8-kv`` runs the FP8-cache study instead (csrc/kernels/attn_extend_d128_fp8.hip):
+(f) the shapes of (d); three arms alternating in one process, timed as in (b): ``ops.attention_extend_gqa_fp8`` on
+    an FP8 cache (e4m3 bytes and fp32 row scales), ``ops.attention_extend_gqa`` on a bf16 cache of the same shape,
+    and ``attention_extend_gqa_fp8_reference`` (the dequantise / bf16 kernel / requantise composition every FP8
+    extend ran before) on the FP8 cache; each arm rotates through its own >= 512 MB of cache copies.  Each line
+    carries the two ratios, the bytes the fp8 kernel must read and the peak memory each fp8 arm allocates above
+    its inputs in one call.
 """
 import argparse
 import json
@@ -225,6 +233,68 @@ def bench_kernel_d128(dev, reps):
                 del data, wide
 
 
+def bench_kernel_fp8kv(dev, reps):
+    import torch
+    from databricks_distributed_deep_learning_amd import ops
+    from databricks_distributed_deep_learning_amd.ops.attention import attention_extend_gqa_fp8_reference as ref_fn
+    D, TS = 128, (16, 64, 128, 512)
+    table = ops.rope_table(8192 + 512, 500000.0, D, dev)
+    for H, Hkv in ((32, 8), (32, 32)):
+        for B in (1, 16):
+            for n in (896, 8191):
+                C = n + max(TS)
+                per_layer = 2 * B * Hkv * C * D
+                L8, L16 = min(64, -(-ROTATE_BYTES // per_layer)), min(64, -(-ROTATE_BYTES // (2 * per_layer)))
+                # any finite e4m3 code (sign | 0 .. 0x77) and scales around 1 / 448: rows of amax about 1
+                c8 = (torch.randint(0, 0x78, (L8, 2, B, Hkv, C, D), device=dev, dtype=torch.uint8)
+                      | (torch.randint(0, 2, (L8, 2, B, Hkv, C, D), device=dev, dtype=torch.uint8) << 7))
+                sc = (torch.rand(L8, 2, B, Hkv, C, device=dev) + 0.5) / 448
+                c16 = torch.randn(L16, 2, B, Hkv, C, D, device=dev).bfloat16()
+                lens = torch.full((B,), n, dtype=torch.int32, device=dev)
+                for T in TS:
+                    qkv = torch.randn(B, T, (H + 2 * Hkv) * D, device=dev).bfloat16()
+
+                    def fp8(k):
+                        j = k % L8
+                        ops.attention_extend_gqa_fp8(qkv, table, c8[j, 0], c8[j, 1], sc[j, 0], sc[j, 1], lens, H, Hkv, n)
+
+                    def bf16(k):
+                        ops.attention_extend_gqa(qkv, table, c16[k % L16, 0], c16[k % L16, 1], lens, H, Hkv, n)
+
+                    def reference(k):
+                        j = k % L8
+                        ref_fn(qkv, table, c8[j, 0], c8[j, 1], sc[j, 0], sc[j, 1], lens, H, Hkv, n)
+
+                    arms = (("fp8", fp8), ("bf16", bf16), ("reference", reference))
+                    iters, peak = {}, {}
+                    for name, fn in arms:       # warm-up (and the call's own allocations); then ~50 ms of calls
+                        torch.cuda.synchronize()
+                        base = torch.cuda.memory_allocated()
+                        torch.cuda.reset_peak_memory_stats()
+                        fn(0)
+                        torch.cuda.synchronize()
+                        peak[name] = torch.cuda.max_memory_allocated() - base
+                        iters[name] = int(min(200, max(3, 5e4 / _events(fn, 3))))
+                    t = {name: [] for name, _ in arms}
+                    for _ in range(reps):
+                        for name, fn in arms:
+                            t[name].append(_events(fn, iters[name]))
+                    t = {name: min(v) for name, v in t.items()}
+                    read = 2 * B * Hkv * n * (D + 4) + B * T * (H + 2 * Hkv) * D * 2 + T * D * 4
+                    print(json.dumps({"kernel": "attention_extend_gqa_d128_fp8", "B": B, "H": H, "Hkv": Hkv, "n": n, "T": T,
+                                      "copies": [L8, L16], "fp8_us": round(t["fp8"], 2), "bf16_us": round(t["bf16"], 2),
+                                      "fp8_reference_us": round(t["reference"], 2),
+                                      "fp8_over_bf16": round(t["fp8"] / t["bf16"], 3),
+                                      "reference_over_fp8": round(t["reference"] / t["fp8"], 2),
+                                      "min_read_MB": round(read / 1e6, 2), "GBps": round(read / t["fp8"] / 1e3, 1),
+                                      "call_peak_MB": round(peak["fp8"] / 2 ** 20, 2),
+                                      "reference_call_peak_MB": round(peak["reference"] / 2 ** 20, 2),
+                                      "floor_bound": bool(t["fp8"] < 1.5 * ENQUEUE_FLOOR_US),
+                                      "faster_than_reference": bool(t["fp8"] < t["reference"]),
+                                      "faster_than_bf16": bool(t["fp8"] < t["bf16"])}), flush=True)
+                del c8, sc, c16
+
+
 def bench_chunked(model, dev, reps):
     import torch
     from databricks_distributed_deep_learning_amd.models import LlamaKVCache
@@ -263,11 +333,16 @@ def main() -> int:
     ap.add_argument("--skip-kernel", action="store_true")
     ap.add_argument("--skip-chunked", action="store_true")
     ap.add_argument("--head-dim", type=int, default=64, choices=(64, 128))
+    ap.add_argument("--fp8-kv", action="store_true")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("llama_extend_bench needs a GPU: times are not measured without one")
     dev = torch.device("cuda", 0)
+    if args.fp8_kv:
+        with torch.no_grad():
+            bench_kernel_fp8kv(dev, args.reps)
+        return 0
     if args.head_dim == 128:
         with torch.no_grad():
             if not args.skip_kernel:

@@ -67,6 +67,7 @@ EXTRA["attn_decode_d128.hip"] = _NO_PK_F32
 EXTRA["attn_extend_d128.hip"] = _NO_PK_F32
 EXTRA["linear_decode_fp8.hip"] = _NO_PK_F32
 EXTRA["attn_decode_d128_fp8.hip"] = _NO_PK_F32
+EXTRA["attn_extend_d128_fp8.hip"] = _NO_PK_F32
 
 
 # Sources whose code decides which GEMM kernel runs fastest for a shape: their hash keys the committed

@@ -35,7 +35,7 @@ there is no position embedding to add); ``generate(prefix=...)`` starts from a c
 An FP8 KV cache (``LlamaKVCache.allocate(fp8=True)``, ``generate(kv_cache_dtype="fp8")``): e4m3 bytes with one fp32
 scale per cached row, half the bytes a decode step streams and half the cache's memory.  ``prefill``, ``decode`` and
 ``extend`` then call ``ops.kv_cache_fill_gqa_fp8``, ``ops.attention_decode_gqa_fp8`` (both native at head dimension
-128) and ``ops.attention_extend_gqa_fp8`` (a torch composition); any other cache runs exactly what it ran before.
+128) and ``ops.attention_extend_gqa_fp8`` (native at head dim 128); any other cache runs exactly what it ran before.
 
 Not covered: ``generate(prefill_chunk=...)`` (chunked prompt consumption is on ``prefill``), ``rope_scaling``,
 sliding-window attention, biased projections.

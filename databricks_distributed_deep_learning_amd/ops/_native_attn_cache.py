@@ -47,6 +47,8 @@ _lib.register({
     "ddl_attn_decode_gqa_d128_fp8_supported": [I, I, I],
     "ddl_attn_decode_gqa_d128_fp8": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, L, CF, P],
     "ddl_kv_cache_fill_gqa_d128_fp8": [P, P, P, P, P, I, I, I, I, I, P],
+    "ddl_attn_extend_gqa_d128_fp8_supported": [I, I],
+    "ddl_attn_extend_gqa_d128_fp8": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, L, CF, P],
 })
 
 _SCALE = 1.0 / math.sqrt(64)
@@ -101,6 +103,13 @@ def supported_decode_fp8(num_heads: int, num_kv_heads: int, head_dim: int = 128)
     """What ``attention_decode_gqa_fp8`` and ``kv_cache_fill_gqa_fp8`` take natively: head dim 128 and the bf16
     kernel's group sizes (csrc/kernels/attn_decode_d128_fp8.hip)."""
     return bool(_lib.fn("ddl_attn_decode_gqa_d128_fp8_supported")(num_heads, num_kv_heads, head_dim))
+
+
+def supported_extend_fp8(num_heads: int, num_kv_heads: int, head_dim: int = 128) -> bool:
+    """What ``attention_extend_gqa_fp8`` takes natively: head dim 128 and the bf16 kernel's group sizes
+    (csrc/kernels/attn_extend_d128_fp8.hip).  Its query tile is the bf16 kernel's: ``tile(..., head_dim=128)``
+    answers for both; its cache tile is 64 keys."""
+    return bool(head_dim == 128 and _lib.fn("ddl_attn_extend_gqa_d128_fp8_supported")(num_heads, num_kv_heads))
 
 
 def tile(T: int, num_heads: int, num_kv_heads: int, head_dim: int = 64) -> int:
@@ -220,3 +229,17 @@ def kv_cache_fill_gqa_fp8(packed, cache_k, cache_v, scale_k, scale_v, num_heads,
     packed = packed.contiguous()
     _lib.call("ddl_kv_cache_fill_gqa_d128_fp8", packed.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(),
               scale_k.data_ptr(), scale_v.data_ptr(), B, S, num_heads, num_kv_heads, cache_k.shape[2])
+
+
+def attention_extend_gqa_fp8(qkv_new, table, cache_k, cache_v, scale_k, scale_v, lens, num_heads, num_kv_heads, max_len,
+                             new_lens=None):
+    """The caller (``ops.attention``) has checked the shapes, dtypes, contiguity and alignment of the four cache
+    tensors."""
+    B, T, H, Hkv = qkv_new.shape[0], qkv_new.shape[1], num_heads, num_kv_heads
+    _check_lens(B, lens, new_lens)
+    qkv_new, table = qkv_new.contiguous(), table.contiguous()
+    out = torch.empty(B, T, H * 128, dtype=qkv_new.dtype, device=qkv_new.device)
+    _lib.call("ddl_attn_extend_gqa_d128_fp8", qkv_new.data_ptr(), table.data_ptr(), cache_k.data_ptr(),
+              cache_v.data_ptr(), scale_k.data_ptr(), scale_v.data_ptr(), lens.data_ptr(), _lib.p(new_lens),
+              out.data_ptr(), B, T, H, Hkv, cache_k.shape[2], max_len, table.shape[0], 1.0 / math.sqrt(128))
+    return out

@@ -532,7 +532,7 @@ def _quantize_rows(x):
     """``x [..., D]`` -> (bytes as uint8 ``[..., D]``, fp32 scales ``[...]``) by ``quantize_fp8_rows``.  On a GPU
     tensor torch forms ``amax / 448`` through a rounded reciprocal, so a scale (and with it a byte) can sit one ulp
     from the format's true division, which the CPU and the native kernels compute: rows written here on the GPU
-    (the references, ``attention_extend_gqa_fp8``) are then not bit-identical to natively written ones.  A row is
+    (the references) are then not bit-identical to natively written ones.  A row is
     always read back with the scale it was stored with."""
     from .linear import quantize_fp8_rows
     q, s = quantize_fp8_rows(x.reshape(-1, x.shape[-1]))
@@ -632,17 +632,17 @@ def kv_cache_fill_gqa_fp8(packed: torch.Tensor, cache_k: torch.Tensor, cache_v: 
     return kv_cache_fill_gqa_fp8_reference(packed, ck, cv, scale_k, scale_v, num_heads, num_kv_heads)
 
 
-def attention_extend_gqa_fp8(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
-                             scale_k: torch.Tensor, scale_v: torch.Tensor, lens: torch.Tensor, num_heads: int,
-                             num_kv_heads: int, max_len: int, new_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``attention_extend_gqa`` on an FP8 cache, as a composition with no kernel of its own: the first
-    ``max_len`` positions are dequantised into a scratch cache of ``max_len + T`` positions in ``qkv_new``'s
-    dtype, ``attention_extend_gqa`` runs on it (native where that op is), and the rows it appended are quantised
-    back with ``quantize_fp8_rows``.  Inside this one call the chunk's own keys and values are therefore seen
-    UNQUANTISED by the chunk's queries; every later call sees them quantised.  On the GPU the write-back is torch's
-    ``quantize_fp8_rows``, whose scales can sit one ulp from the true division of the native fill and decode
-    kernels (``_quantize_rows``): the rows are self-consistent, not bit-identical to natively written ones.
-    Nothing syncs."""
+def attention_extend_gqa_fp8_reference(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: torch.Tensor,
+                                       cache_v: torch.Tensor, scale_k: torch.Tensor, scale_v: torch.Tensor,
+                                       lens: torch.Tensor, num_heads: int, num_kv_heads: int, max_len: int,
+                                       new_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``attention_extend_gqa`` on an FP8 cache as a composition: the first ``max_len`` positions are dequantised
+    into a scratch cache of ``max_len + T`` positions in ``qkv_new``'s dtype, ``attention_extend_gqa`` runs on it
+    (native where that op is), and the rows it appended are quantised back with ``quantize_fp8_rows``.  Inside this
+    one call the chunk's own keys and values are therefore seen UNQUANTISED by the chunk's queries; every later call
+    sees them quantised.  On the GPU the write-back is torch's ``quantize_fp8_rows``, whose scales can sit one ulp
+    from the true division of the native kernels (``_quantize_rows``): the rows are self-consistent, not
+    bit-identical to natively written ones.  Nothing syncs."""
     ck, cv = _fp8_cache_views(cache_k, cache_v, scale_k, scale_v)
     _extend_gqa_guard(qkv_new, table, ck, cv, lens, num_heads, num_kv_heads, max_len, new_lens)
     B, T, dev = qkv_new.shape[0], qkv_new.shape[1], qkv_new.device
@@ -664,3 +664,26 @@ def attention_extend_gqa_fp8(qkv_new: torch.Tensor, table: torch.Tensor, cache_k
         c8[bi, :, pos] = torch.where(real.unsqueeze(-1), q, c8[bi, :, pos])
         scale[bi, :, pos] = torch.where(real, s, scale[bi, :, pos])
     return out
+
+
+def attention_extend_gqa_fp8(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
+                             scale_k: torch.Tensor, scale_v: torch.Tensor, lens: torch.Tensor, num_heads: int,
+                             num_kv_heads: int, max_len: int, new_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``attention_extend_gqa`` on an FP8 cache (e4m3 bytes with one fp32 scale per cached row): the chunk's
+    rotation, attention over the dequantised cached rows and, causally, over the chunk, and the append of the
+    chunk's quantised rows; returns ``[B, T, H·D]``.  Inside this one call the chunk's own keys and values are seen
+    UNQUANTISED by the chunk's queries, on both paths; every later call sees them quantised.  Native at head
+    dimension 128 (csrc/kernels/attn_extend_d128_fp8.hip: bf16 ``qkv_new``, fp32 table, G in 1, 2, 3, 4, 8,
+    16-byte-aligned caches): one launch that reads the cache as bytes and allocates nothing but the output, and
+    whose appended rows are bit-identical to what the native fill and decode kernels would write for the same
+    row.  Everything else runs ``attention_extend_gqa_fp8_reference``.  Nothing syncs."""
+    ck, cv = _fp8_cache_views(cache_k, cache_v, scale_k, scale_v)
+    D = _extend_gqa_guard(qkv_new, table, ck, cv, lens, num_heads, num_kv_heads, max_len, new_lens)
+    if (_lib.use_native(qkv_new, table, ck, cv, scale_k, scale_v, lens, new_lens) and qkv_new.dtype == torch.bfloat16
+            and table.dtype == torch.float32 and D == 128 and ck.data_ptr() % 16 == 0 and cv.data_ptr() % 16 == 0):
+        from . import _native_attn_cache as N
+        if N.supported_extend_fp8(num_heads, num_kv_heads, D):
+            return N.attention_extend_gqa_fp8(qkv_new, table, ck, cv, scale_k, scale_v, lens, num_heads,
+                                              num_kv_heads, max_len, new_lens)
+    return attention_extend_gqa_fp8_reference(qkv_new, table, ck, cv, scale_k, scale_v, lens, num_heads, num_kv_heads,
+                                              max_len, new_lens)
