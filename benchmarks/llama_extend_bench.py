@@ -4,6 +4,7 @@ chunk-attention kernel, chunked prefill.  SmolLM-135M (9 heads over 3 KV heads),
 best of ``--reps`` runs after one warm-up run of each arm, the arms alternating in one process.
 
     python benchmarks/llama_extend_bench.py [--reps 3] [--skip-ttft] [--skip-kernel] [--skip-chunked]
+                                            [--head-dim 128 | --fp8-kv | --split-sweep]
 
 (a) Time to first token (host clock around work that ends in a device synchronise) for an 896-token prefix
     shared by every row plus 64 new tokens, B in {1, 8, 16}: a fresh cache that copies the batch-1 prefix
@@ -25,7 +26,11 @@ best of ``--reps`` runs after one warm-up run of each arm, the arms alternating 
     same tensors (what every D = 128 extend ran before) and the masked SDPA of (b).  Each line carries the bytes
     the kernel must read (n cached K and V rows of Hkv heads, the chunk, its table rows) and the MFMA FLOPs,
     both from the shapes; ``floor_bound`` marks a call time within 1.5x of the ~20 us enqueue floor, which bounds
-    the kernel from above and does not measure it.
+    the kernel from above and does not measure it.  A fourth arm runs the same call with ``key_splits=1`` (the
+    one launch, all there was before the key split): ``one_launch_us``, next to the ``key_splits`` the plan chose.
+    ``--split-sweep`` runs only this comparison, without the reference and SDPA arms: the default, ``key_splits=1``
+    and, at T <= 128, forced ``key_splits`` in {2, 4, 8, 16, 32}, alternating; each line carries the spread of
+    the ``key_splits=1`` arm between its repeats, which is the margin the plan's constants were chosen against.
 (e) (a) for ``llama3_8b(num_hidden_layers=4)``.
 
 ``--fp8-kv`` runs the FP8-cache study instead (csrc/kernels/attn_extend_d128_fp8.hip):
@@ -181,6 +186,7 @@ def bench_kernel_d128(dev, reps):
     import torch
     import torch.nn.functional as F
     from databricks_distributed_deep_learning_amd import ops
+    from databricks_distributed_deep_learning_amd.ops import _native_attn_cache as N
     from databricks_distributed_deep_learning_amd.ops.attention import attention_extend_gqa_reference as ref_fn
     D, TS = 128, (16, 64, 128, 512)
     table = ops.rope_table(8192 + 512, 500000.0, D, dev)
@@ -203,6 +209,10 @@ def bench_kernel_d128(dev, reps):
                     def ours(k):
                         ops.attention_extend_gqa(qkv, table, data[k % L, 0], data[k % L, 1], lens, H, Hkv, n)
 
+                    def one(k):
+                        ops.attention_extend_gqa(qkv, table, data[k % L, 0], data[k % L, 1], lens, H, Hkv, n,
+                                                 key_splits=1)
+
                     def reference(k):
                         ref_fn(qkv, table, data[k % L, 0], data[k % L, 1], lens, H, Hkv, n)
 
@@ -210,7 +220,7 @@ def bench_kernel_d128(dev, reps):
                         F.scaled_dot_product_attention(q, wide[k % L, 0, :, :, :n + T], wide[k % L, 1, :, :, :n + T],
                                                        attn_mask=mask)
 
-                    arms = (("ours", ours), ("reference", reference), ("sdpa", sdpa))
+                    arms = (("ours", ours), ("one", one), ("reference", reference), ("sdpa", sdpa))
                     iters = {}
                     for name, fn in arms:       # warm-up; then as many calls as fit ~50 ms, 3 .. 200
                         fn(0)
@@ -223,7 +233,9 @@ def bench_kernel_d128(dev, reps):
                     flops = 4.0 * B * H * D * T * (n + (T + 1) / 2)
                     read = 2 * B * Hkv * n * D * 2 + B * T * (H + 2 * Hkv) * D * 2 + T * D * 4
                     print(json.dumps({"kernel": "attention_extend_gqa_d128", "B": B, "H": H, "Hkv": Hkv, "n": n, "T": T,
-                                      "copies": L, "us": round(t["ours"], 2), "reference_us": round(t["reference"], 2),
+                                      "copies": L, "us": round(t["ours"], 2),
+                                      "key_splits": N.plan_extend(B, T, H, Hkv, n), "one_launch_us": round(t["one"], 2),
+                                      "reference_us": round(t["reference"], 2),
                                       "sdpa_masked_us": round(t["sdpa"], 2), "min_read_MB": round(read / 1e6, 2),
                                       "mfma_GFLOP": round(flops / 1e9, 3), "TFLOPs": round(flops / t["ours"] / 1e6, 2),
                                       "GBps": round(read / t["ours"] / 1e3, 1),
@@ -231,6 +243,49 @@ def bench_kernel_d128(dev, reps):
                                       "faster_than_reference": bool(t["ours"] < t["reference"]),
                                       "faster_than_sdpa": bool(t["ours"] < t["sdpa"])}), flush=True)
                 del data, wide
+
+
+def bench_split_sweep(dev, reps):
+    import torch
+    from databricks_distributed_deep_learning_amd import ops
+    from databricks_distributed_deep_learning_amd.ops import _native_attn_cache as N
+    D, TS = 128, (16, 64, 128, 512)
+    table = ops.rope_table(8192 + 512, 500000.0, D, dev)
+    for H, Hkv in ((32, 8), (32, 32)):
+        for B in (1, 16):
+            for n in (896, 8191):
+                C = n + max(TS)
+                L = min(64, -(-ROTATE_BYTES // (2 * B * Hkv * C * D * 2)))
+                data = torch.randn(L, 2, B, Hkv, C, D, device=dev).bfloat16()
+                lens = torch.full((B,), n, dtype=torch.int32, device=dev)
+                for T in TS:
+                    qkv = torch.randn(B, T, (H + 2 * Hkv) * D, device=dev).bfloat16()
+
+                    def arm(ks):
+                        return lambda k: ops.attention_extend_gqa(qkv, table, data[k % L, 0], data[k % L, 1], lens, H,
+                                                                  Hkv, n, key_splits=ks)
+
+                    arms = [("default", arm(None)), ("1", arm(1))]
+                    arms += [(str(ks), arm(ks)) for ks in (2, 4, 8, 16, 32)] if T <= 128 else []
+                    iters = {}
+                    for name, fn in arms:
+                        fn(0)
+                        iters[name] = int(min(200, max(3, 5e4 / _events(fn, 3))))
+                    t = {name: [] for name, _ in arms}
+                    for r in range(reps):       # odd rounds backwards: no arm always follows the same neighbour
+                        for name, fn in (arms[::-1] if r % 2 else arms):
+                            t[name].append(_events(fn, iters[name]))
+                    best = {name: round(min(v), 2) for name, v in t.items()}
+                    spread = max(t["1"]) - min(t["1"])
+                    forced = {k: v for k, v in best.items() if k != "default"}
+                    print(json.dumps({"split_sweep": "attention_extend_gqa_d128", "B": B, "H": H, "Hkv": Hkv, "n": n,
+                                      "T": T, "copies": L, "plan": N.plan_extend(B, T, H, Hkv, n), "us": best,
+                                      "one_launch_spread_us": round(spread, 2),
+                                      "default_over_one_launch": round(best["default"] / best["1"], 3),
+                                      "default_minus_best_forced_us": round(best["default"] - min(forced.values()), 2),
+                                      "no_slower_than_one_launch": bool(best["default"] <= best["1"] + spread),
+                                      "floor_bound": bool(best["default"] < 1.5 * ENQUEUE_FLOOR_US)}), flush=True)
+                del data
 
 
 def bench_kernel_fp8kv(dev, reps):
@@ -334,6 +389,7 @@ def main() -> int:
     ap.add_argument("--skip-chunked", action="store_true")
     ap.add_argument("--head-dim", type=int, default=64, choices=(64, 128))
     ap.add_argument("--fp8-kv", action="store_true")
+    ap.add_argument("--split-sweep", action="store_true")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -342,6 +398,10 @@ def main() -> int:
     if args.fp8_kv:
         with torch.no_grad():
             bench_kernel_fp8kv(dev, args.reps)
+        return 0
+    if args.split_sweep:
+        with torch.no_grad():
+            bench_split_sweep(dev, args.reps)
         return 0
     if args.head_dim == 128:
         with torch.no_grad():

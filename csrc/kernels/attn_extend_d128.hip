@@ -68,15 +68,40 @@
 //   again with the same function (the same bits as were scored), values as 16-byte copies.
 //
 // One launch; the grid and the instance follow from B, Hkv, G and T alone; no sync, no atomics, no scratch;
-// nothing this launch stores is read by it; bitwise repeatable.  Not here: a key split over workgroups for a tiny
-// T over a long cache, and a non-rotary D = 128 instance.
+// nothing this launch stores is read by it; bitwise repeatable.  Not here: a non-rotary D = 128 instance.
+//
+//   Key split (ddl_attn_extend_gqa_d128_split; the SPLIT instances of the same kernel, then a merge launch).  The
+//   one launch has ceil(T / TQ) Hkv B workgroups, 8 at B = 1, (32, 8), T = 16, each walking every key tile in turn;
+//   the split form folds a split index into blockIdx.z (b nsplit + s) and gives split s the cache tiles of keys
+//   [s chunk, min((s + 1) chunk, n)), chunk = ceil(max_len / nsplit) rounded up to the tile, so the grid is static
+//   (from max_len) and n = lens[b] is read on the device as before.  A split whose range starts at or past n
+//   returns before it stages anything.  The LAST split is the one that also scores the chunk's own tiles (the
+//   diagonal) and appends, with the code of the one launch, so the appended bits are its bits.  Last, not first:
+//   the first split has a full range of cache keys whenever n >= chunk, and the chunk work on top would make it
+//   the longest workgroup of every row; the last split's range is the shortest (what the rounding of chunk
+//   leaves) and is empty whenever lens[b] is far below max_len, which is exactly when the other splits finish
+//   early too.  It is also the one split that always has a key for every live query (its own), so every live
+//   row has at least one partial.  Staging is unchanged: one tile ahead, same swizzle, chunk K through registers.
+//   Partials: ws is [B, T, H, nsplit][128] fp32 unnormalised accumulators, stored as 16-byte pieces straight from
+//   the MFMA accumulator layout (lane group g owns columns 16 db + 4 g .. + 3 of its query), followed by
+//   [B, T, H, nsplit][2] (running maximum in the exp2 domain, sum).  Only queries i < t of live splits are
+//   written.  Uninitialised workspace cannot reach the result because the merge DERIVES the live splits instead
+//   of reading flags: split s < nsplit - 1 is live iff s chunk < n, the last split always is; it reads those
+//   partials and no others, combines them in split order (M = max m_s, w_s = exp2(m_s - M) with a select to 0 at
+//   m_s = -inf, out = sum w_s O_s / sum w_s l_s, one rounding to bf16) and writes zero bits to rows i >= t.  No
+//   atomics; both launches are bitwise repeatable.  The plan (y_nsplit) is host arithmetic on B, T, H, Hkv and
+//   max_len.
 //
 // Registers.  VGPRs per instance <G, NS>, no scratch in any, 32 KB of LDS each; the launch bounds ask for 4 waves
 // per SIMD from the 8-wave instances (two workgroups per CU), 3 from 4 waves up, 2 below:
-//   <1,1> 206  <1,2> 208  <1,4> 144  <2,1> 208  <2,2> 144  <2,4> 127  <3,1> 200  <3,2> 144  <4,1> 144  <4,2> 127
-//   <8,1> 127.
+//   <1,1> 212  <1,2> 240  <1,4> 160  <2,1> 240  <2,2> 160  <2,4> 126  <3,1> 216  <3,2> 160  <4,1> 160  <4,2> 126
+//   <8,1> 126
+// and the SPLIT instances (scripts/check_spills.py --all-kernels: no scratch in any of the 23 kernels):
+//   <1,1> 211  <1,2> 239  <1,4> 161  <2,1> 239  <2,2> 161  <2,4> 126  <3,1> 216  <3,2> 161  <4,1> 161  <4,2> 126
+//   <8,1> 126; the merge 26, no LDS.
 // So a CU holds two workgroups of the 512-thread instances (<2,4>, <4,2>, <8,1>), of <3,2> and of <3,1>, three of
-// the 256-thread ones, four of <2,1> and <1,2>, and of <1,1> the five that 32 KB of LDS allows.
+// the 256-thread ones, four of <2,1> and <1,2>, and of <1,1> the five that 32 KB of LDS allows; the SPLIT
+// instances have the occupancy of their one-launch twins.
 #include "ddl_lds.h"
 
 #include <algorithm>
@@ -195,11 +220,15 @@ __device__ __forceinline__ bf16x8 pack_p(const f32x4& a, const f32x4& b) {
     return r;
 }
 
-template <int G, int NS>
+// SPLIT: the key-split form (see the header).  blockIdx.z is b nsplit + s; split s walks the cache tiles of keys
+// [s chunk, min((s + 1) chunk, n)), the last split also the chunk's own tiles and the append; every split stores
+// fp32 partials to ws instead of rows of out.  Without SPLIT the three last arguments are not read.
+template <int G, int NS, bool SPLIT>
 __global__ __launch_bounds__(64 * G * NS, (G * NS >= 8 ? 4 : (G * NS >= 4 ? 3 : 2))) void attn_extend_d128_k(
     const bf16_t* __restrict__ qkv, const float* __restrict__ tab, bf16_t* __restrict__ kcache,
     bf16_t* __restrict__ vcache, const int* __restrict__ lens, const int* __restrict__ new_lens,
-    bf16_t* __restrict__ out, int T, int Hkv, int C, int max_len, float scale) {
+    bf16_t* __restrict__ out, int T, int Hkv, int C, int max_len, float scale, float* __restrict__ ws, int nsplit,
+    int chunk) {
     constexpr int NW = G * NS, NT = 64 * NW, TQ = 16 * NS;
     // a chunk K tile is rotated in units of W columns and their partners: 256 pairs (W = 8), or 512 half-pairs
     // (W = 4) in the 512-thread instances, where pairs would leave half the waves idle and cost all of them 24
@@ -209,7 +238,9 @@ __global__ __launch_bounds__(64 * G * NS, (G * NS >= 8 ? 4 : (G * NS >= 4 ? 3 : 
     constexpr int NU = (UNITS + NT - 1) / NT;
     constexpr bool ARRIVE = NU > 2;
     __shared__ __attribute__((aligned(16))) char smem[4 * YIMG];   // K0 V0 K1 V1
-    const int qt = (int)(gridDim.x - 1 - blockIdx.x), hkv = blockIdx.y, b = blockIdx.z;   // longest loop first
+    const int qt = (int)(gridDim.x - 1 - blockIdx.x), hkv = blockIdx.y;                   // longest loop first
+    const int b = SPLIT ? (int)blockIdx.z / nsplit : (int)blockIdx.z, sp = SPLIT ? (int)blockIdx.z % nsplit : 0;
+    const bool last = !SPLIT || sp == nsplit - 1;               // the split with the chunk's own keys and the append
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4;
     const int hg = wv / NS, sub = wv % NS;      // this wave's query head of the group and its 16-query sub-tile
     const int H = Hkv * G, h = hkv * G + hg;
@@ -229,7 +260,15 @@ __global__ __launch_bounds__(64 * G * NS, (G * NS >= 8 ? 4 : (G * NS >= 4 ? 3 : 
     const int q0 = qt * TQ, q0w = q0 + 16 * sub, myq = q0w + (lane & 15);
     bf16_t* orow = out + ((long)b * T + myq) * HD + (long)h * YD + 4 * g;
 
-    if (q0 >= tl) {     // padded queries only: zeros, nothing to append
+    // this split's cache tiles ct0 .. ct0 + nc - 1 (chunk is a multiple of the tile, so only n cuts a tile)
+    const int ct0 = SPLIT ? sp * (chunk / YTK) : 0;
+    const int nc = SPLIT ? max(0, (min((sp + 1) * chunk, n) + YTK - 1) / YTK - ct0) : (n + YTK - 1) / YTK;
+    if constexpr (SPLIT) {
+        // a split past n stages nothing and stores nothing (the merge knows it from lens[b]); rows >= tl are the
+        // merge's zeros
+        if ((!last && nc == 0) || q0 >= tl) return;
+    }
+    if (!SPLIT && q0 >= tl) {     // padded queries only: zeros, nothing to append
         if (myq < T) {
 #pragma unroll
             for (int db = 0; db < 8; ++db) *reinterpret_cast<uint2*>(orow + 16 * db) = make_uint2(0u, 0u);
@@ -240,25 +279,27 @@ __global__ __launch_bounds__(64 * G * NS, (G * NS >= 8 ? 4 : (G * NS >= 4 ? 3 : 
     // append, once per KV head: this workgroup's chunk positions q0 .. q0 + TQ - 1 (those < tl).  The keys: 8
     // pairs per position, rotated once more instead of read back from LDS (the same function, so the same
     // bits); the values: 16-byte bit copies, 16 per position
+    if (last) {
 #pragma unroll
-    for (int i = 0; i < (8 * TQ + NT - 1) / NT; ++i) {
-        const int unit = tid + i * NT;
-        if ((8 * TQ) % NT == 0 || unit < 8 * TQ) {
-            const int j = q0 + (unit >> 3), jc = min(j, tl - 1), c8 = unit & 7;
-            const RotIn<8> ri = rot_load<8>(kb + (long)jc * rs, tb + (long)jc * YD, c8);
-            uint32_t lo[4], hi[4];
-            rot_apply<8>(ri, lo, hi);
-            if (j < tl) {
-                stw<8>(ck + (long)(n + j) * YD + 8 * c8, lo);
-                stw<8>(ck + (long)(n + j) * YD + YH + 8 * c8, hi);
+        for (int i = 0; i < (8 * TQ + NT - 1) / NT; ++i) {
+            const int unit = tid + i * NT;
+            if ((8 * TQ) % NT == 0 || unit < 8 * TQ) {
+                const int j = q0 + (unit >> 3), jc = min(j, tl - 1), c8 = unit & 7;
+                const RotIn<8> ri = rot_load<8>(kb + (long)jc * rs, tb + (long)jc * YD, c8);
+                uint32_t lo[4], hi[4];
+                rot_apply<8>(ri, lo, hi);
+                if (j < tl) {
+                    stw<8>(ck + (long)(n + j) * YD + 8 * c8, lo);
+                    stw<8>(ck + (long)(n + j) * YD + YH + 8 * c8, hi);
+                }
             }
         }
-    }
 #pragma unroll
-    for (int i = 0; i < (16 * TQ + NT - 1) / NT; ++i) {
-        const int piece = tid + i * NT;
-        const int j = q0 + (piece >> 4), s16 = piece & 15;
-        if (piece < 16 * TQ && j < tl) st16(cv + (long)(n + j) * YD + s16 * 8, ld16(vb + (long)j * rs + s16 * 8));
+        for (int i = 0; i < (16 * TQ + NT - 1) / NT; ++i) {
+            const int piece = tid + i * NT;
+            const int j = q0 + (piece >> 4), s16 = piece & 15;
+            if (piece < 16 * TQ && j < tl) st16(cv + (long)(n + j) * YD + s16 * 8, ld16(vb + (long)j * rs + s16 * 8));
+        }
     }
 
     // Q fragments (B operand of S^T = K Q^T): lane holds Q[myq][32 kk + 8 g + 0..7], rotated: fragments kk and
@@ -277,8 +318,8 @@ __global__ __launch_bounds__(64 * G * NS, (G * NS >= 8 ? 4 : (G * NS >= 4 ? 3 : 
         }
     }
 
-    const int nc = (n + YTK - 1) / YTK;                         // cache tiles
-    const int nd = min(q0 + TQ - 1, tl - 1) / YTK + 1;           // chunk tiles, through the workgroup's last diagonal one
+    // chunk tiles, through the workgroup's last diagonal one (none in a split that is not the last)
+    const int nd = last ? min(q0 + TQ - 1, tl - 1) / YTK + 1 : 0;
     const int ntot = nc + nd;
     RotIn<W> kin[ARRIVE ? 1 : NU];                               // the next chunk K tile's units, in flight
     // unit -> its chunk row (clamped: a clamped row rotates by its clamped position) and its loads
@@ -290,8 +331,8 @@ __global__ __launch_bounds__(64 * G * NS, (G * NS >= 8 ? 4 : (G * NS >= 4 ? 3 : 
     auto stage = [&](int i, int buf) __attribute__((always_inline)) {
         char* sK = smem + buf * 2 * YIMG;
         if (i < nc) {
-            dma_tile<NW>(ck, YD, i * YTK, n, sK, wv, lane);
-            dma_tile<NW>(cv, YD, i * YTK, n, sK + YIMG, wv, lane);
+            dma_tile<NW>(ck, YD, (ct0 + i) * YTK, n, sK, wv, lane);
+            dma_tile<NW>(cv, YD, (ct0 + i) * YTK, n, sK + YIMG, wv, lane);
         } else {
             const int row0 = (i - nc) * YTK;
             dma_tile<NW>(vb, rs, row0, tl, sK + YIMG, wv, lane);
@@ -350,7 +391,7 @@ __global__ __launch_bounds__(64 * G * NS, (G * NS >= 8 ? 4 : (G * NS >= 4 ? 3 : 
         // (none after the last tile: LDS-DMA must not be landing when the workgroup exits)
         if (i + 1 < ntot) stage(i + 1, (i + 1) & 1);
         const bool cache = i < nc;
-        const int key0 = (cache ? i : i - nc) * YTK;
+        const int key0 = (cache ? ct0 + i : i - nc) * YTK;
         // a chunk tile that starts past this wave's last query holds nothing for it (key0 and q0w are multiples
         // of 16, so key0 <= q0w + 15 is key0 <= q0w: every query of a scoring wave sees key key0)
         if (active && (cache || key0 <= q0w)) {
@@ -412,6 +453,18 @@ __global__ __launch_bounds__(64 * G * NS, (G * NS >= 8 ? 4 : (G * NS >= 4 ? 3 : 
     }
     lsum += __shfl_xor(lsum, 16, 64);
     lsum += __shfl_xor(lsum, 32, 64);
+    if constexpr (SPLIT) {
+        // the partial of (b, myq, h, sp), straight from the accumulator layout: lane group g holds columns
+        // 16 db + 4 g .. + 3.  ws is [rows][128] accumulators, then [rows][2] (maximum, sum), rows = B T H nsplit.
+        // Every query < tl of a split that gets here has scored a key (a cache tile of its range, or its diagonal)
+        if (myq >= tl) return;
+        const long row = (((long)b * T + myq) * H + h) * nsplit + sp;
+        float* po = ws + row * YD + 4 * g;
+#pragma unroll
+        for (int db = 0; db < 8; ++db) *reinterpret_cast<f32x4*>(po + 16 * db) = o[db];
+        if (g == 0) *reinterpret_cast<float2*>(ws + (long)gridDim.z * T * H * YD + row * 2) = make_float2(m, lsum);
+        return;
+    }
     if (myq >= T) return;
     const bool qok = myq < tl;                                   // (then lsum >= 1: its own key)
     const float inv = qok ? 1.f / lsum : 0.f;
@@ -421,6 +474,45 @@ __global__ __launch_bounds__(64 * G * NS, (G * NS >= 8 ? 4 : (G * NS >= 4 ? 3 : 
                             qok ? o[db][3] * inv : 0.f};
         store4(orow + 16 * db, v);
     }
+}
+
+// The merge of a split launch: 32 threads per (b, query i, head h), 4 columns each, 8 rows per workgroup.  The live
+// splits of a row follow from lens[b] and chunk (cache splits 0 .. ceil(n / chunk) - 1 below the last, and the
+// last); they are combined in split order, nothing else of ws is read.  Rows i >= t are zero bits.
+__global__ __launch_bounds__(256) void attn_extend_d128_merge_k(const float* __restrict__ ws,
+                                                                const int* __restrict__ lens,
+                                                                const int* __restrict__ new_lens,
+                                                                bf16_t* __restrict__ out, long rows, int T, int H,
+                                                                int nsplit, int chunk, int max_len) {
+    const long row = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
+    if (row >= rows) return;
+    const int c = threadIdx.x & 31, b = (int)(row / ((long)T * H)), i = (int)(row / H % T);
+    const int n = min(max(lens[b], 0), max_len);
+    const int tl = new_lens ? min(max(new_lens[b], 1), T) : T;
+    bf16_t* po = out + row * YD + 4 * c;
+    if (i >= tl) {
+        *reinterpret_cast<uint2*>(po) = make_uint2(0u, 0u);
+        return;
+    }
+    const int nlive = min(nsplit - 1, (n + chunk - 1) / chunk);
+    const float2* ml = reinterpret_cast<const float2*>(ws + rows * nsplit * YD) + row * nsplit;
+    const float* acc = ws + row * nsplit * YD + 4 * c;
+    float M = ml[nsplit - 1].x;
+    for (int s = 0; s < nlive; ++s) M = fmaxf(M, ml[s].x);
+    float l = 0.f, o[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < nsplit; ++s) {
+        if (s >= nlive && s != nsplit - 1) continue;
+        const float2 p = ml[s];
+        const float w = p.x == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(p.x - M);    // (never -inf - -inf)
+        float v[4];
+        load4(acc + (long)s * YD, v);
+        l += w * p.y;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] += w * v[k];
+    }
+    const float inv = 1.f / l;
+    const float r[4] = {o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv};
+    store4(po, r);
 }
 
 inline bool y_group_ok(int H, int Hkv) {
@@ -435,6 +527,27 @@ inline int y_subtiles(int T, int G) {
     const int want = T <= 16 ? 1 : (T <= 32 ? 2 : 4);
     const int cap = G >= 8 ? 1 : (G >= 3 ? 2 : 4);
     return std::min(want, cap);
+}
+
+// Keys per split of a launch of nsplit splits over a bound of max_len keys: a multiple of the key tile
+inline int y_chunk(int max_len, int nsplit) {
+    const int per = (std::max(max_len, 1) + nsplit - 1) / nsplit;
+    return (per + YTK - 1) / YTK * YTK;
+}
+
+// The plan: key splits of the launch, from the shapes and max_len alone.  Enough splits that there are two
+// workgroups per CU, at most Y_MAX_SPLIT, each of at least Y_MIN_KEYS keys (7 tiles; so max_len below 448 is
+// always the one launch).  The two per CU, the cap (the largest value tried) and the minimum are read off the
+// sweep in profiles/llama_d128_extend_split.log
+constexpr int Y_MAX_SPLIT = 32, Y_MIN_KEYS = 224;
+inline int y_nsplit(int B, int T, int H, int Hkv, int max_len) {
+    if (!y_group_ok(H, Hkv) || B < 1 || T < 1) return 1;
+    const int tq = 16 * y_subtiles(T, H / Hkv);
+    const long wgs = (long)((T + tq - 1) / tq) * Hkv * B;
+    const long want = std::min<long>({Y_MAX_SPLIT, (2 * num_cus() + wgs - 1) / wgs, max_len / Y_MIN_KEYS});
+    if (want < 2) return 1;
+    const int chunk = y_chunk(max_len, (int)want);
+    return std::max(1, (max_len + chunk - 1) / chunk);          // (no split that max_len leaves empty)
 }
 
 }  // namespace
@@ -455,9 +568,9 @@ DDL_API int ddl_attn_extend_gqa_d128(const void* qkv_new, const float* tab, void
         return (int)hipErrorInvalidValue;
     const int G = H / Hkv;
 #define Y_LAUNCH(G_, NS_)                                                                                              \
-    attn_extend_d128_k<G_, NS_><<<dim3((T + 16 * NS_ - 1) / (16 * NS_), Hkv, B), 64 * G_ * NS_, 0, st>>>(              \
+    attn_extend_d128_k<G_, NS_, false><<<dim3((T + 16 * NS_ - 1) / (16 * NS_), Hkv, B), 64 * G_ * NS_, 0, st>>>(       \
         (const bf16_t*)qkv_new, tab, (bf16_t*)kcache, (bf16_t*)vcache, (const int*)lens, (const int*)new_lens,         \
-        (bf16_t*)out, T, Hkv, C, max_len, scale)
+        (bf16_t*)out, T, Hkv, C, max_len, scale, nullptr, 1, 0)
     switch (G * 8 + y_subtiles(T, G)) {
         case 1 * 8 + 1: Y_LAUNCH(1, 1); break;
         case 1 * 8 + 2: Y_LAUNCH(1, 2); break;
@@ -473,5 +586,53 @@ DDL_API int ddl_attn_extend_gqa_d128(const void* qkv_new, const float* tab, void
         default: return (int)hipErrorInvalidValue;
     }
 #undef Y_LAUNCH
+    DDL_RETURN_LAUNCH();
+}
+
+// key splits the plan gives this shape (1: the one launch above)
+DDL_API int ddl_attn_extend_gqa_d128_nsplit(int B, int T, int H, int Hkv, int max_len) {
+    return y_nsplit(B, T, H, Hkv, max_len);
+}
+// floats of workspace a launch of nsplit splits needs
+DDL_API long ddl_attn_extend_gqa_d128_ws(int B, int T, int H, int nsplit) {
+    return (long)B * T * H * nsplit * (2 + YD);
+}
+
+// The key-split form: nsplit >= 2 splits of y_chunk(max_len, nsplit) keys, then the merge; ws holds
+// ddl_attn_extend_gqa_d128_ws(B, T, H, nsplit) floats and need not be initialised.
+DDL_API int ddl_attn_extend_gqa_d128_split(const void* qkv_new, const float* tab, void* kcache, void* vcache,
+                                           const void* lens, const void* new_lens, void* out, void* ws, int nsplit,
+                                           int B, int T, int H, int Hkv, int C, int max_len, long n_pos, float scale,
+                                           hipStream_t st) {
+    if (!y_group_ok(H, Hkv)) return (int)hipErrorInvalidValue;
+    if (B <= 0 || T <= 0) return 0;
+    if (max_len < 0 || (long)max_len + T > C || (long)max_len + T > n_pos || Hkv > 65535 || nsplit < 2 || !ws ||
+        (long)B * nsplit > 65535)
+        return (int)hipErrorInvalidValue;
+    const int G = H / Hkv, chunk = y_chunk(max_len, nsplit);
+#define Y_LAUNCH(G_, NS_)                                                                                              \
+    attn_extend_d128_k<G_, NS_, true><<<dim3((T + 16 * NS_ - 1) / (16 * NS_), Hkv, B * nsplit), 64 * G_ * NS_, 0,      \
+                                        st>>>((const bf16_t*)qkv_new, tab, (bf16_t*)kcache, (bf16_t*)vcache,           \
+                                              (const int*)lens, (const int*)new_lens, (bf16_t*)out, T, Hkv, C,         \
+                                              max_len, scale, (float*)ws, nsplit, chunk)
+    switch (G * 8 + y_subtiles(T, G)) {
+        case 1 * 8 + 1: Y_LAUNCH(1, 1); break;
+        case 1 * 8 + 2: Y_LAUNCH(1, 2); break;
+        case 1 * 8 + 4: Y_LAUNCH(1, 4); break;
+        case 2 * 8 + 1: Y_LAUNCH(2, 1); break;
+        case 2 * 8 + 2: Y_LAUNCH(2, 2); break;
+        case 2 * 8 + 4: Y_LAUNCH(2, 4); break;
+        case 3 * 8 + 1: Y_LAUNCH(3, 1); break;
+        case 3 * 8 + 2: Y_LAUNCH(3, 2); break;
+        case 4 * 8 + 1: Y_LAUNCH(4, 1); break;
+        case 4 * 8 + 2: Y_LAUNCH(4, 2); break;
+        case 8 * 8 + 1: Y_LAUNCH(8, 1); break;
+        default: return (int)hipErrorInvalidValue;
+    }
+#undef Y_LAUNCH
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
+    const long rows = (long)B * T * H;
+    attn_extend_d128_merge_k<<<(unsigned)((rows + 7) / 8), 256, 0, st>>>(
+        (const float*)ws, (const int*)lens, (const int*)new_lens, (bf16_t*)out, rows, T, H, nsplit, chunk, max_len);
     DDL_RETURN_LAUNCH();
 }

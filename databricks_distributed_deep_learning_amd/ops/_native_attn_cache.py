@@ -44,6 +44,9 @@ _lib.register({
     "ddl_attn_extend_gqa_d128_supported": [I, I],
     "ddl_attn_extend_gqa_d128_tile": [I, I, I],
     "ddl_attn_extend_gqa_d128": [P, P, P, P, P, P, P, I, I, I, I, I, I, L, CF, P],
+    "ddl_attn_extend_gqa_d128_nsplit": [I, I, I, I, I],
+    "ddl_attn_extend_gqa_d128_ws": [I, I, I, I],
+    "ddl_attn_extend_gqa_d128_split": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, L, CF, P],
     "ddl_attn_decode_gqa_d128_fp8_supported": [I, I, I],
     "ddl_attn_decode_gqa_d128_fp8": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, L, CF, P],
     "ddl_kv_cache_fill_gqa_d128_fp8": [P, P, P, P, P, I, I, I, I, I, P],
@@ -66,6 +69,16 @@ def plan_gqa(B: int, Hkv: int, max_len: int):
     the 16 of a D = 128 one)."""
     return (_lib.fn("ddl_attn_decode_gqa_nsplit")(B, Hkv, max_len),
             _lib.fn("ddl_attn_decode_gqa_chunk")(B, Hkv, max_len))
+
+
+def plan_extend(B: int, T: int, num_heads: int, num_kv_heads: int, max_len: int, head_dim: int = 128) -> int:
+    """Key splits ``attention_extend_gqa`` uses by default: from the shapes and ``max_len`` alone, like
+    ``plan_gqa``.  1 is the one launch: at head dim 64 (no split there), without an instance for the group size,
+    and for every ``max_len`` below 448.  More than 1 when the one launch's ``ceil(T / tile) Hkv B`` workgroups
+    are fewer than two per CU over a long cache: each split walks ``ceil(max_len / nsplit)`` keys rounded up to 32."""
+    if head_dim != 128:
+        return 1
+    return _lib.fn("ddl_attn_extend_gqa_d128_nsplit")(B, T, num_heads, num_kv_heads, max_len)
 
 
 def supported(num_heads: int, num_kv_heads: int, head_dim: int = 64) -> bool:
@@ -132,7 +145,7 @@ def _check_cache(cache_k, cache_v, B, heads, name="H", dims=(64,)):
 
 
 def _workspace(ws_fn: str, dev, *args):
-    """The fp32 partials buffer of a split decode launch (None with one split)."""
+    """The fp32 partials buffer of a split launch (None with one split)."""
     f = _lib.fn(ws_fn)
     f.restype = L
     n = f(*args)
@@ -178,7 +191,10 @@ def attention_extend(qkv_new, cache_k, cache_v, lens, num_heads, max_len, new_le
     return out
 
 
-def attention_extend_gqa(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len, new_lens=None):
+def attention_extend_gqa(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len, new_lens=None,
+                         key_splits=None):
+    """``key_splits``: None for ``plan_extend``'s answer, 1 for the one launch, n >= 2 for that many key splits and
+    the merge launch (head dim 128 only; head dim 64 has the one launch)."""
     B, T, H, Hkv = qkv_new.shape[0], qkv_new.shape[1], num_heads, num_kv_heads
     D = _check_cache(cache_k, cache_v, B, Hkv, "Hkv", DECODE_HEAD_DIMS)
     if qkv_new.shape[2] != (H + 2 * Hkv) * D or table.shape[1] != D:
@@ -187,6 +203,13 @@ def attention_extend_gqa(qkv_new, table, cache_k, cache_v, lens, num_heads, num_
     _check_lens(B, lens, new_lens)
     qkv_new, table = qkv_new.contiguous(), table.contiguous()
     out = torch.empty(B, T, H * D, dtype=qkv_new.dtype, device=qkv_new.device)
+    nsplit = 1 if D == 64 else (plan_extend(B, T, H, Hkv, max_len) if key_splits is None else key_splits)
+    if nsplit > 1:
+        ws = _workspace("ddl_attn_extend_gqa_d128_ws", qkv_new.device, B, T, H, nsplit)
+        _lib.call("ddl_attn_extend_gqa_d128_split", qkv_new.data_ptr(), table.data_ptr(), cache_k.data_ptr(),
+                  cache_v.data_ptr(), lens.data_ptr(), _lib.p(new_lens), out.data_ptr(), _lib.p(ws), nsplit, B, T, H,
+                  Hkv, cache_k.shape[2], max_len, table.shape[0], 1.0 / math.sqrt(D))
+        return out
     _lib.call("ddl_attn_extend_gqa" if D == 64 else "ddl_attn_extend_gqa_d128", qkv_new.data_ptr(), table.data_ptr(),
               cache_k.data_ptr(), cache_v.data_ptr(), lens.data_ptr(), _lib.p(new_lens), out.data_ptr(), B, T, H, Hkv,
               cache_k.shape[2], max_len, table.shape[0], 1.0 / math.sqrt(D))

@@ -486,11 +486,21 @@ def attention_extend_gqa_reference(qkv_new: torch.Tensor, table: torch.Tensor, c
 
 def attention_extend_gqa(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
                          lens: torch.Tensor, num_heads: int, num_kv_heads: int, max_len: int,
-                         new_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+                         new_lens: Optional[torch.Tensor] = None, key_splits: Optional[int] = None) -> torch.Tensor:
     """Grouped-query causal attention of a chunk of new tokens over the rotated cache plus the chunk, with the
     chunk's rotation and the append; returns ``[B, T, H·D]``.  Native at head dimension 64 and 128 (bf16, G in 1, 2,
     3, 4, 8; csrc/kernels/attn_extend.hip and attn_extend_d128.hip); every other case is the reference, which may
-    share a cache with the kernels (``_native_attn_cache.supported_decode`` says why that is sound)."""
+    share a cache with the kernels (``_native_attn_cache.supported_decode`` says why that is sound).
+
+    ``key_splits`` is how many workgroups share the cached keys of one (query tile, KV head, batch row) on the
+    native head-dim-128 path, each writing fp32 partials that a second launch merges in a fixed order: ``None``
+    (the default) lets ``_native_attn_cache.plan_extend`` decide from the shapes and ``max_len`` -- a short chunk
+    over a long cache is split, everything with ``max_len`` below 448 is not --, 1 is always the one launch,
+    n >= 2 forces n splits.  The appended cache rows do not depend on it; the output does in its last bits.  On the
+    reference path and at head dimension 64 a valid value is accepted and has no effect.  Anything but None or an
+    integer >= 1 is a ``ValueError``."""
+    if key_splits is not None and (isinstance(key_splits, bool) or not isinstance(key_splits, int) or key_splits < 1):
+        raise ValueError(f"key_splits must be None or an integer >= 1, got {key_splits!r}")
     D = _extend_gqa_guard(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len, new_lens)
     if (_lib.use_native(qkv_new, table, cache_k, cache_v, lens, new_lens) and qkv_new.dtype == torch.bfloat16
             and cache_k.dtype == torch.bfloat16 and cache_v.dtype == torch.bfloat16
@@ -498,7 +508,7 @@ def attention_extend_gqa(qkv_new: torch.Tensor, table: torch.Tensor, cache_k: to
         from . import _native_attn_cache as N
         if N.supported_extend(num_heads, num_kv_heads, D):
             return N.attention_extend_gqa(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len,
-                                          new_lens)
+                                          new_lens, key_splits)
     return attention_extend_gqa_reference(qkv_new, table, cache_k, cache_v, lens, num_heads, num_kv_heads, max_len,
                                           new_lens)
 
